@@ -20,6 +20,13 @@ cv=5, on 1M x 100 tabular data, 1/2/4/8 MI355X (one rank per GPU, RCCL over xGMI
 
 Run: ``python bench.py [--gpus N --steps K --warmup W]`` (N>1 under torchrun, or it
 re-launches itself through torch.distributed.run before touching the GPU).
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+``--dump-outputs DIR`` also writes what the last timed step returned (``DIR/*.npy``) so
+two builds can be compared output for output.  ``--full`` adds the secondary figures:
+per-rank fit times, measured and LPT-predicted step imbalance, and the per-phase
+summary on stderr.  ``--config lr`` and ``--e2e`` are other workloads with their own
+result lines; they only run when asked for.
 """
 from __future__ import annotations
 
@@ -52,6 +59,33 @@ def _relaunch(args) -> int:
     return subprocess.call(cmd, env=env)
 
 
+def _dump_outputs(out_dir: str, arrays: dict) -> None:
+    """``--dump-outputs``: one ``<name>.npy`` per array, float32 / float64 only, 64 MB at most."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        total += a.nbytes
+        if total > 64 * 1024 * 1024:
+            raise RuntimeError(f"--dump-outputs: {name} takes the dump past 64 MB")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def _result_arrays(ids, res) -> dict:
+    """What ``run_candidates`` handed this rank for the candidates ``ids``: the scores only
+    (its timings differ from run to run and are not outputs)."""
+    import numpy as np
+
+    return {"rank0_candidate_ids": np.asarray(ids, dtype=np.float64),
+            "rank0_cv_scores": np.asarray([x.result["cv_scores"] for x in res], dtype=np.float64).reshape(len(ids), -1),
+            "rank0_mean_cv_score": np.asarray([x.result["mean_cv_score"] for x in res], dtype=np.float64),
+            "rank0_std_cv_score": np.asarray([x.result["std_cv_score"] for x in res], dtype=np.float64)}
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -72,6 +106,12 @@ def main() -> int:
                     help="the whole 256 x 5 grid as ONE J1 job through Controller + runner (LocalRunner at N=1, "
                          "the cluster DistributedRunner at N>1), incl. holdout fits and the refit")
     ap.add_argument("--chunk-target-s", type=float, default=None, help="e2e: runner slice size (estimated seconds)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the score table every "
+                         "rank receives, rank 0's own results) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also report the secondary figures: per-rank fit times, measured and LPT-predicted step "
+                         "imbalance, the per-phase summary on stderr (a plain run reports the headline only)")
     args = ap.parse_args()
 
     if args.rows is None:
@@ -171,7 +211,7 @@ def main() -> int:
 
     def step(s: int):
         mine = rank_step_cands(s)
-        if N > 1:
+        if N > 1 and args.full:
             pool = step_pool(s)
             owner = lpt_assign([float(costs[i]) for i in pool], N)
             per = np.zeros(N)
@@ -200,6 +240,7 @@ def main() -> int:
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
+    last = None
     for s in range(args.warmup, args.warmup + args.steps):
         last = step(s)
     if dev.type == "cuda":
@@ -215,9 +256,16 @@ def main() -> int:
     # per-rank step times (N > 1 diagnosis: a poor curve says whether the placement or the
     # ranks' speed is to blame)
     timed = list(range(args.warmup, args.warmup + args.steps))
-    bt = torch.tensor([busy.get(s, 0.0) for s in timed], dtype=torch.float64, device=dev)
-    all_bt = dist.all_gather_rows(bt.view(1, -1)).cpu().numpy()          # [N, steps]
+    if args.full:
+        bt = torch.tensor([busy.get(s, 0.0) for s in timed], dtype=torch.float64, device=dev)
+        all_bt = dist.all_gather_rows(bt.view(1, -1)).cpu().numpy()          # [N, steps]
     if r == 0:
+        if args.dump_outputs and last is not None:
+            # the last timed step's result path: the score table (row i = candidate_ids[i]) as
+            # every rank holds it after the all-reduce, and rank 0's own run_candidates results
+            _dump_outputs(args.dump_outputs, {"candidate_ids": np.asarray(step_pool(timed[-1]), dtype=np.float64),
+                                              "cv_scores": score_buf.cpu().numpy(),
+                                              **_result_arrays(rank_step_cands(timed[-1]), last)})
         mean_cv = float(score_buf.mean().item())
         out = {
             "metric": "CV-fits/sec (whole node), 256-pt RF GridSearchCV on 1M×100 tabular",
@@ -243,15 +291,18 @@ def main() -> int:
             },
             "setup_s": round(setup_s, 2),
             "mean_cv_accuracy_last_step": round(mean_cv, 4),
-            "per_rank_fit_ms_per_step": {"min": round(1000 * float(all_bt.mean(1).min()), 1),
-                                         "mean": round(1000 * float(all_bt.mean(1).mean()), 1),
-                                         "max": round(1000 * float(all_bt.mean(1).max()), 1)},
-            "measured_step_imbalance": round(float(np.mean(all_bt.max(0) / np.maximum(all_bt.mean(0), 1e-12))), 3),
-            "lpt_predicted_imbalance": round(float(np.mean([lpt_imb[s] for s in timed])), 3) if N > 1 else 1.0,
             "device": str(torch.cuda.get_device_name(dev)) if dev.type == "cuda" else "cpu",
         }
+        if args.full:
+            out.update({
+                "per_rank_fit_ms_per_step": {"min": round(1000 * float(all_bt.mean(1).min()), 1),
+                                             "mean": round(1000 * float(all_bt.mean(1).mean()), 1),
+                                             "max": round(1000 * float(all_bt.mean(1).max()), 1)},
+                "measured_step_imbalance": round(float(np.mean(all_bt.max(0) / np.maximum(all_bt.mean(0), 1e-12))), 3),
+                "lpt_predicted_imbalance": round(float(np.mean([lpt_imb[s] for s in timed])), 3) if N > 1 else 1.0,
+            })
+            print("phases:", json.dumps(trace.summary()), file=sys.stderr, flush=True)
         line = json.dumps(out)
-        print("phases:", json.dumps(trace.summary()), file=sys.stderr, flush=True)
         print(line, flush=True)
         if args.json_out:
             with open(args.json_out, "w") as f:
@@ -326,8 +377,9 @@ def run_lr(args) -> int:
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        step()
+        last = step()
     if dev.type == "cuda":
         torch.cuda.synchronize(dev)
     dist.barrier()
@@ -337,10 +389,16 @@ def run_lr(args) -> int:
     fits = len(cands) * args.cv
     value = args.steps * fits / elapsed
     if r == 0:
-        from cs230_distributed_machine_learning_amd.utils import trace
+        if args.dump_outputs and last is not None:
+            import numpy as np
 
-        print("phases:", json.dumps(trace.summary()), file=sys.stderr, flush=True)
-        print("solve:", json.dumps(stats), file=sys.stderr, flush=True)
+            _dump_outputs(args.dump_outputs, {"candidate_ids": np.arange(len(cands), dtype=np.float64),
+                                              "cv_scores": score_buf.cpu().numpy(), **_result_arrays(mine, last)})
+        if args.full:
+            from cs230_distributed_machine_learning_amd.utils import trace
+
+            print("phases:", json.dumps(trace.summary()), file=sys.stderr, flush=True)
+            print("solve:", json.dumps(stats), file=sys.stderr, flush=True)
         line = {
             "metric": "CV-fits/sec (whole node), RandomizedSearchCV LogisticRegression n_iter=512 cv=5 on 10M×1000",
             "value": round(value, 4), "unit": "CV-fits/s", "n_gpus": N, "steps": args.steps, "warmup": args.warmup,
@@ -490,9 +548,16 @@ def run_e2e(args) -> int:
         "slices": out["slices"], "fits_per_slice_mean": round(out["fits_per_slice_mean"], 1),
         "slice_wall_sum_s": round(out["slice_wall_sum_s"], 2),
     }
-    from cs230_distributed_machine_learning_amd.utils import trace
+    if args.dump_outputs:
+        import numpy as np
 
-    print("phases:", json.dumps(trace.summary()), file=sys.stderr, flush=True)
+        _dump_outputs(args.dump_outputs, {
+            "cv_scores": np.asarray([r.get("cv_scores", []) for r in res], dtype=np.float64),
+            "mean_cv_score": np.asarray([r.get("mean_cv_score", math.nan) for r in res], dtype=np.float64)})
+    if args.full:
+        from cs230_distributed_machine_learning_amd.utils import trace
+
+        print("phases:", json.dumps(trace.summary()), file=sys.stderr, flush=True)
     print(json.dumps(line), flush=True)
     if args.json_out:
         with open(args.json_out, "w") as f:
