@@ -11,7 +11,10 @@
 // Work per level is bucketed by node size so every node gets a right-sized worker:
 //   * wave tier  (count <= wave_max):  one 64-lane wave per node; LDS histogram,
 //     wave-scan over the 256 bins, wave-argmax, ballot-based stable partition — one
-//     fused kernel, no global histogram traffic;
+//     fused kernel, no global histogram traffic.  Binary classification with wave_max <= 255
+//     (the caller's default): one 32-bit word per bin (w0 | w1 << 12 | rows << 24, forest_common.h
+//     pack_bin32) -- 1 KB of LDS per feature, 32-bit LDS atomics, DPP scans and field extraction
+//     (DML_WAVE_HIST32); nodes of 256 rows and more go to the block tier;
 //   * block tier (count <= block_max): one 256-thread workgroup per node, same fused
 //     pipeline with 4 waves evaluating features in parallel;
 //   * large tier (count > block_max):  per (node, row-chunk) workgroups build LDS
@@ -96,6 +99,19 @@ template <int MODE> constexpr int block_nt() { return MODE == 1 ? DML_BLOCK_NT :
 #endif
 #ifndef DML_KGMAX_WAVE
 #define DML_KGMAX_WAVE 4
+#endif
+#ifndef DML_WAVE_HIST32
+// wave tier, binary classification, nodes of <= 255 rows: the fused node kernel's histogram word
+// is ONE u32 (forest_common.h pack_bin32: 12/12/8-bit fields) instead of the u64 -- 1 KB of LDS
+// per feature, 32-bit LDS atomics, DPP scans and field extraction.  0: the u64 kernel (A/B builds)
+#define DML_WAVE_HIST32 1
+#endif
+#ifndef DML_KGMAX_WAVE32
+// feature-group bound of the narrow-word wave kernel (pk[] registers): the caller's default group
+// (ops/forest_ops.py kg_wave_bin = 5).  At 8 (1 KB each: the u64 kernel's LDS, two rounds for
+// max_features = 10) the sweep build was 0.4 % slower than at 5 and the generic-criterion
+// instantiation spills 96 B of scratch instead of 72 (docs/WAVE_HIST32.md); A/B builds may raise it
+#define DML_KGMAX_WAVE32 5
 #endif
 #ifndef DML_ROW_WINDOWS
 #define DML_ROW_WINDOWS 1      // block tier: whole-row dwordx4 loads for the first feature group (d <= 112)
@@ -492,7 +508,9 @@ __device__ int make_children(const Ctx& c, int node, int feat, int bin, const do
 // histogram modes
 // ------------------------------------------------------------------------------------
 // MODE 0: classification, C class planes + 1 row-count plane of uint32 [CH][256]
-// MODE 1: binary classification, ONE uint64 plane: (w0 | w1 << 21 | rows << 42)
+// MODE 1: binary classification, ONE uint64 plane: (w0 | w1 << 21 | rows << 42); the wave tier's
+//         fused kernel narrows it to ONE uint32 plane (w0 | w1 << 12 | rows << 24) for its
+//         <= 255-row nodes (k_nodes H32) -- the block, large and big-subtree tiers keep the u64
 // MODE 2: regression, float planes (sum w, sum wy, sum wy^2, rows) [4][256]
 template <int MODE> struct HT;
 template <> struct HT<0> { using T = uint32_t; };
@@ -538,11 +556,11 @@ __device__ __forceinline__ void scan256(CT* p, int lane) {
 }
 
 // channel `ch` (CH layout: classes.., rows / s0,s1,s2,rows) of cumulative bin b
-template <int MODE>
-__device__ __forceinline__ double hist_chan(const typename HT<MODE>::T* h, int ch, int CH, int b) {
+template <int MODE, class CT = typename HT<MODE>::T>
+__device__ __forceinline__ double hist_chan(const CT* h, int ch, int CH, int b) {
   if constexpr (MODE == 1) {
-    const unsigned long long v = h[b];
-    return (double)(ch == 2 ? (v >> 42) : ((v >> (21 * ch)) & kPackMask21));
+    const CT v = h[b];
+    return (double)(ch == 2 ? pk_rows<CT>(v) : (ch == 1 ? pk_w1<CT>(v) : pk_w0<CT>(v)));
   } else {
     return (double)h[ch * 256 + b];
   }
@@ -575,11 +593,12 @@ __device__ __forceinline__ bool gini_pf_ok(const NodeSpec& s, double cw0, double
 // A candidate whose own bin is empty is skipped: its cumulative channels equal the previous
 // bin's, which wins the tie (lowest bin), so the split chosen is unchanged; what is left is
 // usually one contender per lane, re-scored in one pass.
-template <int NF, int FS>
-__device__ DML_EVAL_ATTR void eval_gini_pf(unsigned long long* h, int span, const NodeSpec& s, int lane,
+// CT: the packed word, u64 (21/21/22-bit fields) or the wave tier's u32 (12/12/8, pack_bin32).
+template <int NF, int FS, class CT = unsigned long long>
+__device__ DML_EVAL_ATTR void eval_gini_pf(CT* h, int span, const NodeSpec& s, int lane,
                                            double* out_gain, int* out_bin, int* out_nc, double* out_left, int CH,
                                            bool zero_after, double cw0, double cw1) {
-  uint64_t v[NF][4];
+  CT v[NF][4];
 #pragma unroll
   for (int f = 0; f < NF; ++f)
 #pragma unroll
@@ -588,21 +607,24 @@ __device__ DML_EVAL_ATTR void eval_gini_pf(unsigned long long* h, int span, cons
 #pragma unroll
     for (int f = 0; f < NF; ++f)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) h[f * FS * span + 4 * lane + i] = 0ull;
+      for (int i = 0; i < 4; ++i) h[f * FS * span + 4 * lane + i] = (CT)0;
   }
   uint32_t nz[NF];
 #pragma unroll
   for (int f = 0; f < NF; ++f) {
-    nz[f] = (v[f][0] != 0ull ? 1u : 0u) | (v[f][1] != 0ull ? 2u : 0u) | (v[f][2] != 0ull ? 4u : 0u) |
-            (v[f][3] != 0ull ? 8u : 0u);
+    nz[f] = (v[f][0] != (CT)0 ? 1u : 0u) | (v[f][1] != (CT)0 ? 2u : 0u) | (v[f][2] != (CT)0 ? 4u : 0u) |
+            (v[f][3] != (CT)0 ? 8u : 0u);
     v[f][1] += v[f][0]; v[f][2] += v[f][1]; v[f][3] += v[f][2];
   }
-  uint64_t t[NF];
-#pragma unroll
-  for (int f = 0; f < NF; ++f) t[f] = wave::incl_scan_u64(v[f][3]);
+  CT t[NF];
 #pragma unroll
   for (int f = 0; f < NF; ++f) {
-    const uint64_t ex = wave::excl_from_incl<uint64_t>(t[f]);
+    if constexpr (sizeof(CT) == 8) t[f] = (CT)wave::incl_scan_u64((uint64_t)v[f][3]);
+    else t[f] = wave::incl_scan<CT>(v[f][3]);
+  }
+#pragma unroll
+  for (int f = 0; f < NF; ++f) {
+    const CT ex = wave::excl_from_incl<CT>(t[f]);
 #pragma unroll
     for (int i = 0; i < 4; ++i) v[f][i] += ex;
   }
@@ -614,16 +636,16 @@ __device__ DML_EVAL_ATTR void eval_gini_pf(unsigned long long* h, int span, cons
   bool nc[NF];
 #pragma unroll
   for (int f = 0; f < NF; ++f) {
-    const uint64_t tv = wave::bcast<uint64_t>(t[f], 63);
-    tr[f] = (uint32_t)(tv >> 42); t0i[f] = (uint32_t)(tv & kPackMask21); t1i[f] = (uint32_t)((tv >> 21) & kPackMask21);
+    const CT tv = wave::bcast<CT>(t[f], 63);
+    tr[f] = pk_rows<CT>(tv); t0i[f] = pk_w0<CT>(tv); t1i[f] = pk_w1<CT>(tv);
     const double t0 = (double)t0i[f] * cw0, t1 = (double)t1i[f] * cw1;
     qm[f] = -INFINITY;
     nc[f] = false;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const uint64_t cv = v[f][i];
-      const uint32_t rl = (uint32_t)(cv >> 42), rr = tr[f] - rl;
-      const uint32_t l0i = (uint32_t)(cv & kPackMask21), l1i = (uint32_t)((cv >> 21) & kPackMask21);
+      const CT cv = v[f][i];
+      const uint32_t rl = pk_rows<CT>(cv), rr = tr[f] - rl;
+      const uint32_t l0i = pk_w0<CT>(cv), l1i = pk_w1<CT>(cv);
       nc[f] |= (rl > 0u && rr > 0u);
       bool ok = ((nz[f] >> i) & 1u) && (lane * 4 + i) != 255 && rl >= mslu && rr >= mslu;
       if (mwl) {
@@ -653,8 +675,8 @@ __device__ DML_EVAL_ATTR void eval_gini_pf(unsigned long long* h, int span, cons
       if (m != 0u) {
         const int i = __builtin_ctz(m);
         m &= m - 1u;
-        const uint64_t cv = i == 0 ? v[f][0] : i == 1 ? v[f][1] : i == 2 ? v[f][2] : v[f][3];
-        const double l0 = (double)(cv & kPackMask21) * cw0, l1 = (double)((cv >> 21) & kPackMask21) * cw1;
+        const CT cv = i == 0 ? v[f][0] : i == 1 ? v[f][1] : i == 2 ? v[f][2] : v[f][3];
+        const double l0 = (double)pk_w0<CT>(cv) * cw0, l1 = (double)pk_w1<CT>(cv) * cw1;
         ClsAcc L, R;
         L.init(kGini); R.init(kGini);
         L.add(l0); L.add(l1);
@@ -673,13 +695,13 @@ __device__ DML_EVAL_ATTR void eval_gini_pf(unsigned long long* h, int span, cons
     }
     const bool any_nc = __ballot(nc[f]) != 0ull;
     const int src = bb >= 0 ? (bb >> 2) : 0, sel = bb >= 0 ? (bb & 3) : 0;
-    const uint64_t mine = sel == 0 ? v[f][0] : sel == 1 ? v[f][1] : sel == 2 ? v[f][2] : v[f][3];
-    const uint64_t cv = wave::bcast<uint64_t>(mine, src);
+    const CT mine = sel == 0 ? v[f][0] : sel == 1 ? v[f][1] : sel == 2 ? v[f][2] : v[f][3];
+    const CT cv = wave::bcast<CT>(mine, src);
     if (lane == 0) {
       double* ol = out_left + f * FS * CH;
-      ol[0] = bb >= 0 ? (double)(cv & kPackMask21) * cw0 : 0.0;
-      ol[1] = bb >= 0 ? (double)((cv >> 21) & kPackMask21) * cw1 : 0.0;
-      ol[2] = bb >= 0 ? (double)(cv >> 42) : 0.0;
+      ol[0] = bb >= 0 ? (double)pk_w0<CT>(cv) * cw0 : 0.0;
+      ol[1] = bb >= 0 ? (double)pk_w1<CT>(cv) * cw1 : 0.0;
+      ol[2] = bb >= 0 ? (double)pk_rows<CT>(cv) : 0.0;
       out_gain[f * FS] = best; out_bin[f * FS] = bb; out_nc[f * FS] = any_nc ? 1 : 0;
     }
   }
@@ -690,18 +712,17 @@ __device__ DML_EVAL_ATTR void eval_gini_pf(unsigned long long* h, int span, cons
 // arg-maxed without writing the scan back to LDS; the histogram is cleared by the same
 // lanes right after the read.  Multiclass (MODE 0) keeps the LDS path (C+1 planes).
 // RP: regression planes present (3, or 2 without the y^2 plane: out_left[2] is then 0)
-template <int MODE, int RP = 3>
-__device__ DML_EVAL_ATTR void eval_feature(typename HT<MODE>::T* h, int C, int CH, const NodeSpec& s, int lane,
+template <int MODE, int RP = 3, class CT = typename HT<MODE>::T>
+__device__ DML_EVAL_ATTR void eval_feature(CT* h, int C, int CH, const NodeSpec& s, int lane,
                              double* out_gain, int* out_bin, int* out_nc, double* out_left, bool zero_after,
                              const double* cw = nullptr, const RegScale* rq = nullptr, MonoQ mq = MonoQ{0, 0.0, 0.0},
                              double* out_mid = nullptr) {
   if constexpr (MODE == 0) {
     eval_feature_lds<MODE>(h, C, CH, s, lane, out_gain, out_bin, out_nc, out_left, zero_after, cw, mq, out_mid);
   } else {
-    using CT = typename HT<MODE>::T;
     if constexpr (MODE == 1) {
       if (mq.m == 0 && gini_pf_ok(s, cwk(cw, 0), cwk(cw, 1))) {
-        eval_gini_pf<1, 1>(h, 256, s, lane, out_gain, out_bin, out_nc, out_left, CH, zero_after, cwk(cw, 0), cwk(cw, 1));
+        eval_gini_pf<1, 1, CT>(h, 256, s, lane, out_gain, out_bin, out_nc, out_left, CH, zero_after, cwk(cw, 0), cwk(cw, 1));
         if (out_mid && lane == 0) *out_mid = 0.0;
         return;
       }
@@ -738,7 +759,7 @@ __device__ DML_EVAL_ATTR void eval_feature(typename HT<MODE>::T* h, int C, int C
     int bb = -1;
     bool nc = false;
     double tot_rows;
-    if constexpr (MODE == 1) tot_rows = (double)((uint64_t)tot[0] >> 42);
+    if constexpr (MODE == 1) tot_rows = (double)pk_rows<CT>(tot[0]);
     else tot_rows = reg_rows(tot[0]);
     // binary Gini: fp32 pre-filter.  Every candidate bin is scored in fp32 (relative error
     // < 2^-19: all terms are sums and products of non-negative values), and only the bins
@@ -750,9 +771,7 @@ __device__ DML_EVAL_ATTR void eval_feature(typename HT<MODE>::T* h, int C, int C
     if constexpr (MODE == 1 && DML_GINI_PF)
       pf = s.criterion == kGini && mq.m == 0 && cw0 >= 0x1p-20 && cw0 <= 0x1p20 && cw1 >= 0x1p-20 && cw1 <= 0x1p20;
     if (MODE == 1 && pf) {
-      const uint64_t tv = (uint64_t)tot[0];
-      const uint32_t trows = (uint32_t)(tv >> 42), t0i = (uint32_t)(tv & kPackMask21),
-                     t1i = (uint32_t)((tv >> 21) & kPackMask21);
+      const uint32_t trows = pk_rows<CT>(tot[0]), t0i = pk_w0<CT>(tot[0]), t1i = pk_w1<CT>(tot[0]);
       const uint32_t mslu = (uint32_t)s.min_samples_leaf;
       const float cw0f = (float)cw0, cw1f = (float)cw1;
       const double t0 = (double)t0i * cw0, t1 = (double)t1i * cw1;
@@ -761,9 +780,9 @@ __device__ DML_EVAL_ATTR void eval_feature(typename HT<MODE>::T* h, int C, int C
       float qmax = -INFINITY;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const uint64_t cv = (uint64_t)v[0][i];
-        const uint32_t rl = (uint32_t)(cv >> 42), rr = trows - rl;
-        const uint32_t l0i = (uint32_t)(cv & kPackMask21), l1i = (uint32_t)((cv >> 21) & kPackMask21);
+        const CT cv = v[0][i];
+        const uint32_t rl = pk_rows<CT>(cv), rr = trows - rl;
+        const uint32_t l0i = pk_w0<CT>(cv), l1i = pk_w1<CT>(cv);
         nc |= (rl > 0u && rr > 0u);
         bool ok = (lane * 4 + i) != 255 && rl >= mslu && rr >= mslu;
         if (mwl) {   // the generic path's side weights, same doubles
@@ -782,8 +801,8 @@ __device__ DML_EVAL_ATTR void eval_feature(typename HT<MODE>::T* h, int C, int C
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         if (!(q[i] >= thr) || q[i] == -INFINITY) continue;
-        const uint64_t cv = (uint64_t)v[0][i];
-        const double l0 = (double)(cv & kPackMask21) * cw0, l1 = (double)((cv >> 21) & kPackMask21) * cw1;
+        const CT cv = v[0][i];
+        const double l0 = (double)pk_w0<CT>(cv) * cw0, l1 = (double)pk_w1<CT>(cv) * cw1;
         ClsAcc L, R;
         L.init(s.criterion); R.init(s.criterion);
         L.add(l0); L.add(l1);
@@ -796,7 +815,7 @@ __device__ DML_EVAL_ATTR void eval_feature(typename HT<MODE>::T* h, int C, int C
     for (int i = 0; i < 4; ++i) {
       const int b = lane * 4 + i;
       double rl;
-      if constexpr (MODE == 1) rl = (double)((uint64_t)v[0][i] >> 42);
+      if constexpr (MODE == 1) rl = (double)pk_rows<CT>(v[0][i]);
       else rl = reg_rows(v[0][i]);
       const double rr = tot_rows - rl;
       if (b == 255) continue;
@@ -804,9 +823,9 @@ __device__ DML_EVAL_ATTR void eval_feature(typename HT<MODE>::T* h, int C, int C
       if (rl < msl || rr < msl) continue;
       double g, mid = 0.0;
       if constexpr (MODE == 1) {
-        const uint64_t cv = (uint64_t)v[0][i], tv = (uint64_t)tot[0];
-        const double l0 = (double)(cv & kPackMask21) * cw0, l1 = (double)((cv >> 21) & kPackMask21) * cw1;
-        const double t0 = (double)(tv & kPackMask21) * cw0, t1 = (double)((tv >> 21) & kPackMask21) * cw1;
+        const CT cv = v[0][i], tv = tot[0];
+        const double l0 = (double)pk_w0<CT>(cv) * cw0, l1 = (double)pk_w1<CT>(cv) * cw1;
+        const double t0 = (double)pk_w0<CT>(tv) * cw0, t1 = (double)pk_w1<CT>(tv) * cw1;
         ClsAcc L, R;
         L.init(s.criterion); R.init(s.criterion);
         L.add(l0); L.add(l1);
@@ -844,14 +863,14 @@ __device__ DML_EVAL_ATTR void eval_feature(typename HT<MODE>::T* h, int C, int C
     // the winning bin's cumulative channels, broadcast from its owner lane
     const int src = bb >= 0 ? (bb >> 2) : 0, sel = bb >= 0 ? (bb & 3) : 0;
     if constexpr (MODE == 1) {
-      uint64_t mine = (uint64_t)v[0][0];
+      CT mine = v[0][0];
 #pragma unroll
-      for (int i = 1; i < 4; ++i) if (sel == i) mine = (uint64_t)v[0][i];
-      const uint64_t cv = wave::bcast<uint64_t>(mine, src);
+      for (int i = 1; i < 4; ++i) if (sel == i) mine = v[0][i];
+      const CT cv = wave::bcast<CT>(mine, src);
       if (lane == 0) {
-        out_left[0] = bb >= 0 ? (double)(cv & kPackMask21) * cw0 : 0.0;
-        out_left[1] = bb >= 0 ? (double)((cv >> 21) & kPackMask21) * cw1 : 0.0;
-        out_left[2] = bb >= 0 ? (double)(cv >> 42) : 0.0;
+        out_left[0] = bb >= 0 ? (double)pk_w0<CT>(cv) * cw0 : 0.0;
+        out_left[1] = bb >= 0 ? (double)pk_w1<CT>(cv) * cw1 : 0.0;
+        out_left[2] = bb >= 0 ? (double)pk_rows<CT>(cv) : 0.0;
       }
     } else {
       uint64_t mine[NP];
@@ -1148,12 +1167,15 @@ __device__ __forceinline__ PRaw payload_fetch(const Ctx& c, const float* ty, uin
   return r;
 }
 
-template <int MODE, bool PK = false>
-__device__ __forceinline__ typename PLT<MODE>::T payload_finish(const Ctx& c, const NodeSpec& s, const float* ty,
-                                                                const PRaw& r) {
+// PL: the payload type -- PLT<MODE>::T, or uint32_t for the wave tier's narrow binary word
+template <int MODE, bool PK = false, class PL = typename PLT<MODE>::T>
+__device__ __forceinline__ PL payload_finish(const Ctx& c, const NodeSpec& s, const float* ty, const PRaw& r) {
   if constexpr (MODE == 2) {
     const uint32_t w = (PK || c.packed) ? (r.wd >> c.rbits) & 15u : boot_weight(s, r.wd);
     return reg_payload(c, w, r.y);
+  } else if constexpr (MODE == 1 && sizeof(PL) == 4) {
+    if (!PK && !c.packed) return pack_bin32(c.ycls[r.wd], boot_weight(s, r.wd));
+    return pack_bin32((int)(r.wd >> (c.rbits + 4)), (r.wd >> c.rbits) & 15u);
   } else {
     return word_payload<MODE, PK>(c, s, ty, r.wd);
   }
@@ -1193,10 +1215,11 @@ __device__ __forceinline__ void hist_add_wy(typename HT<MODE>::T* hj, int b, con
   if constexpr (MODE == 2) atomicAdd(&hj[wo + b], pl.wy);
 }
 
-template <int MODE, int RP = 3>
-__device__ __forceinline__ void hist_add(typename HT<MODE>::T* hj, const Ctx& c, int b, const typename PLT<MODE>::T& pl) {
+// CT / PL: deduced -- the mode's word and payload, or u32 both for the narrow binary word
+template <int MODE, int RP = 3, class CT = typename HT<MODE>::T, class PL = typename PLT<MODE>::T>
+__device__ __forceinline__ void hist_add(CT* hj, const Ctx& c, int b, const PL& pl) {
 #ifdef DML_X2_ATOMIC   // sensitivity build: every histogram atomic issued twice (the second adds 0)
-  if constexpr (MODE == 1) atomicAdd(&hj[b], (unsigned long long)(pl * (uint64_t)((uint32_t)c.n >> 31)));
+  if constexpr (MODE == 1) atomicAdd(&hj[b], (CT)(pl * (PL)((uint32_t)c.n >> 31)));
 #endif
   if constexpr (MODE == 2) {
     atomicAdd(&hj[b], pl.wr);
@@ -1208,20 +1231,22 @@ __device__ __forceinline__ void hist_add(typename HT<MODE>::T* hj, const Ctx& c,
     atomicAdd(&hj[(int)(uint32_t)pl * 256 + b], (uint32_t)(pl >> 32));
     atomicAdd(&hj[c.C * 256 + b], 1u);
   } else if constexpr (MODE == 1) {
-    atomicAdd(&hj[b], (unsigned long long)pl);
+    atomicAdd(&hj[b], (CT)pl);
   }
 }
 
-template <int NT, int MODE, int FC>
+// H32 (wave tier of a binary build whose wave_max <= kPack32MaxRows): the narrow u32 word
+template <int NT, int MODE, int FC, bool H32 = false>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? DML_NODES_WPE_REG : (MODE == 0 ? DML_NODES_WPE_MC : (NT == 64 ? DML_NODES_WPE_WAVE : DML_NODES_WPE)), (MODE == 1 && NT == 64) ? DML_NODES_WPE_WAVE_MAX : 8))) void k_nodes(Ctx c, int tier, int set_cur,
                                                                                                    int pair_base, int stage_base) {
-  using CT = typename HT<MODE>::T;
+  static_assert(!H32 || (MODE == 1 && NT == 64), "the narrow word is the binary wave tier's");
+  using CT = typename std::conditional<H32, uint32_t, typename HT<MODE>::T>::type;
   constexpr bool PK = FC >= 0;   // specialised builds have packed row words
   constexpr int NW = NT / 64;
   constexpr int RPT = NT == 64 ? 4 : DML_RPT_BLOCK;   // rows per thread in registers (<= 4: packed u8 x 4)
   static_assert(RPT >= 1 && RPT <= 4, "RPT");
   static_assert(2 * RPT * (NT / 64) <= 32, "Scratch::wcnt too small for this NT x RPT");
-  constexpr int KGMAX = NT == 64 ? DML_KGMAX_WAVE : DML_KGMAX_BLOCK;   // feature-group bound (register-resident bins)
+  constexpr int KGMAX = NT == 64 ? (H32 ? DML_KGMAX_WAVE32 : DML_KGMAX_WAVE) : DML_KGMAX_BLOCK;   // feature-group bound (register-resident bins)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   PH_BEGIN
   const OpenNode on = c.open[set_cur][tier][blockIdx.x];
@@ -1263,9 +1288,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
   // for every feature group and the partition; larger nodes stream in NT*RPT chunks.
   // (block tier, DML_BLOCK_STREAM_ONLY: nodes there have > wave_max >= NT rows, so the
   // register-rows paths are compiled out of it -- their registers no longer bound its occupancy)
-  const bool reg_rows = (NT > 64 && DML_BLOCK_STREAM_ONLY) ? false : cnt <= NT * RPT;
+  // (narrow word: the launcher sends it only builds with wave_max <= kPack32MaxRows < NT * RPT)
+  const bool reg_rows = (NT > 64 && DML_BLOCK_STREAM_ONLY) ? false : (H32 || cnt <= NT * RPT);
   uint32_t rrow[RPT], rbin[RPT];
-  using PL = typename PLT<MODE>::T;
+  using PL = typename std::conditional<H32, uint32_t, typename PLT<MODE>::T>::type;
   PL rpl[RPT];
   PRaw rpr[RPT];
   // row ids, then the payload loads (payload_fetch: unconditional, so they stay counted in
@@ -1284,7 +1310,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
   auto finish_rows = [&]() {
 #pragma unroll
     for (int u = 0; u < RPT; ++u)
-      rpl[u] = rrow[u] != 0xFFFFFFFFu ? payload_finish<MODE, PK>(c, s, ty, rpr[u]) : PL{};
+      rpl[u] = rrow[u] != 0xFFFFFFFFu ? payload_finish<MODE, PK, PL>(c, s, ty, rpr[u]) : PL{};
   };
   if (reg_rows) load_rows(0);
 #pragma unroll
@@ -1423,7 +1449,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
             *(uint4*)(c.bscr + (on.start + base + tid) * 16) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
           }
           if (valid) {
-            const PL pl = payload_finish<MODE, PK>(c, s, ty, pr);
+            const PL pl = payload_finish<MODE, PK, PL>(c, s, ty, pr);
 #pragma unroll
             for (int j = 0; j < G; ++j)
               if (j < g) hist_add<MODE>(hist + j * span, c, (int)b[j], pl);
@@ -1489,7 +1515,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
                 make_uint4(b[0], NPK > 1 ? b[NPK > 1 ? 1 : 0] : 0u, NPK > 2 ? b[NPK > 2 ? 2 : 0] : 0u,
                            NPK > 3 ? b[NPK > 3 ? 3 : 0] : 0u);
           if (valid) {
-            const PL pl = payload_finish<MODE, PK>(c, s, ty, pr);
+            const PL pl = payload_finish<MODE, PK, PL>(c, s, ty, pr);
 #pragma unroll
             for (int j = 0; j < G; ++j)
               if (j < g) hist_add<MODE>(hist + j * span, c, (int)((b[j >> 2] >> (8 * (j & 3))) & 0xFFu), pl);
@@ -1607,7 +1633,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
       if (gini_pf_ok(s, cwk(cw, 0), cwk(cw, 1)))
         for (; j0 + NW < g; j0 += 2 * NW) {
           if (mono_of<FC>(c, s, feats[j0]) != 0 || mono_of<FC>(c, s, feats[j0 + NW]) != 0) break;
-          eval_gini_pf<2, NW>(hist + j0 * span, span, s, lane, rg + j0, rb + j0, rn + j0, rleft + j0 * c.CH, c.CH, true,
+          eval_gini_pf<2, NW, CT>(hist + j0 * span, span, s, lane, rg + j0, rb + j0, rn + j0, rleft + j0 * c.CH, c.CH, true,
                               cwk(cw, 0), cwk(cw, 1));
           if (lane == 0) { rmid[j0] = 0.0; rmid[j0 + NW] = 0.0; }
         }
@@ -1615,11 +1641,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
 #endif
     for (int j = j0; j < g; j += NW) {
 #ifdef DML_X2_EVAL   // sensitivity build: every feature evaluated twice (the first keeps the histogram)
-      eval_feature<MODE>(hist + j * span, c.C, c.CH, s, lane, rg + j, rb + j, rn + j, rleft + j * c.CH, false,
+      eval_feature<MODE, 3, CT>(hist + j * span, c.C, c.CH, s, lane, rg + j, rb + j, rn + j, rleft + j * c.CH, false,
                          tree_cw<FC>(c, on.tree), &c.rq, MonoQ{mono_of<FC>(c, s, feats[j]), sc->lo, sc->hi}, rmid + j);
       wave_lds_sync();
 #endif
-      eval_feature<MODE>(hist + j * span, c.C, c.CH, s, lane, rg + j, rb + j, rn + j, rleft + j * c.CH, true,
+      eval_feature<MODE, 3, CT>(hist + j * span, c.C, c.CH, s, lane, rg + j, rb + j, rn + j, rleft + j * c.CH, true,
                          tree_cw<FC>(c, on.tree), &c.rq, MonoQ{mono_of<FC>(c, s, feats[j]), sc->lo, sc->hi}, rmid + j);
     }
     __syncthreads();
@@ -4090,6 +4116,8 @@ const char* dml_forest_last_error(int* line) {
   return hipGetErrorString(g_last_err);
 }
 
+// 1: binary builds with wave_max <= 255 run the narrow-word wave kernel (DML_WAVE_HIST32)
+int dml_forest_wave_hist32() { return DML_WAVE_HIST32 != 0 ? 1 : 0; }
 int dml_forest_sizeof_treespec() { return (int)sizeof(TreeSpec); }
 int dml_forest_sizeof_args() { return (int)sizeof(ForestArgs); }
 int dml_forest_sizeof_node() { return (int)sizeof(NodeRec); }
@@ -4154,7 +4182,12 @@ static int build_impl(ForestArgs* a, hipStream_t st) {
   const size_t lds_s = sub_lds(a);
   const size_t lds_s32 = sub_lds(a, 32);
   const size_t lds_sub_f = sub_lds(a, 64, true), lds_sub32_f = sub_lds(a, 32, true);   // k_subtree<REG, FCX>
-  const size_t lds_w = fused_lds(a, (int)a->kg_wave);
+  // binary wave tier: the narrow-word kernel whenever no wave-tier node can exceed its 255 rows
+  // (the caller clamps wave_max for binary builds; a larger DML_TIER_WAVE_MAX keeps the u64 kernel)
+  constexpr bool kH32 = MODE == 1 && DML_WAVE_HIST32 != 0;
+  const bool h32 = kH32 && !big && a->wave_max <= kPack32MaxRows;
+  const size_t lds_w = h32 ? fused_layout((int)std::min<int64_t>(a->kg_wave, DML_KGMAX_WAVE32), 256, 4, c.CH).total + 16
+                           : fused_lds(a, (int)std::min<int64_t>(a->kg_wave, DML_KGMAX_WAVE));   // the kernels' KG
   const size_t lds_b = fused_lds(a, (int)std::min<int64_t>(a->kg_block, DML_KGMAX_BLOCK));   // the kernel's KG
   const int CH = c.CH;
   // k_hist_large's dynamic LDS, optionally padded (DML_LARGE_LDS_MIN bytes) to cap its
@@ -4185,6 +4218,10 @@ static int build_impl(ForestArgs* a, hipStream_t st) {
       HIP_OK(hipFuncSetAttribute((const void*)k_subtree<REG, FCX>, hipFuncAttributeMaxDynamicSharedMemorySize, need));
       HIP_OK(hipFuncSetAttribute((const void*)k_nodes<64, MODE, -1>, hipFuncAttributeMaxDynamicSharedMemorySize, need));
       HIP_OK(hipFuncSetAttribute((const void*)k_nodes<64, MODE, FCX>, hipFuncAttributeMaxDynamicSharedMemorySize, need));
+      if constexpr (kH32) {
+        HIP_OK(hipFuncSetAttribute((const void*)k_nodes<64, MODE, -1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, need));
+        HIP_OK(hipFuncSetAttribute((const void*)k_nodes<64, MODE, FCX, true>, hipFuncAttributeMaxDynamicSharedMemorySize, need));
+      }
       HIP_OK(hipFuncSetAttribute((const void*)k_nodes<block_nt<MODE>(), MODE, -1>, hipFuncAttributeMaxDynamicSharedMemorySize, need));
       HIP_OK(hipFuncSetAttribute((const void*)k_nodes<block_nt<MODE>(), MODE, FCX>, hipFuncAttributeMaxDynamicSharedMemorySize, need));
       HIP_OK(hipFuncSetAttribute((const void*)k_hist_large<MODE, false>, hipFuncAttributeMaxDynamicSharedMemorySize, need));
@@ -4255,6 +4292,7 @@ static int build_impl(ForestArgs* a, hipStream_t st) {
       if (nw) {
         if constexpr (MODE == 1) {
           if (big) k_bigsub<FCX><<<nw, 256, lds_big, s1>>>(c, cur);
+          else if (h32) k_nodes<64, MODE, FCX, kH32><<<nw, 64, lds_w, s1>>>(c, 1, cur, (int)pair_w, 0);
           else k_nodes<64, MODE, FCX><<<nw, 64, lds_w, s1>>>(c, 1, cur, (int)pair_w, 0);
         } else {
           k_nodes<64, MODE, FCX><<<nw, 64, lds_w, s1>>>(c, 1, cur, (int)pair_w, 0);
@@ -4267,6 +4305,7 @@ static int build_impl(ForestArgs* a, hipStream_t st) {
       if (nw) {
         if constexpr (MODE == 1) {
           if (big) k_bigsub<-1><<<nw, 256, lds_big, s1>>>(c, cur);
+          else if (h32) k_nodes<64, MODE, -1, kH32><<<nw, 64, lds_w, s1>>>(c, 1, cur, (int)pair_w, 0);
           else k_nodes<64, MODE, -1><<<nw, 64, lds_w, s1>>>(c, 1, cur, (int)pair_w, 0);
         } else {
           k_nodes<64, MODE, -1><<<nw, 64, lds_w, s1>>>(c, 1, cur, (int)pair_w, 0);

@@ -175,6 +175,40 @@ DML_HD uint64_t pack_bin(int cls, uint32_t w) {
   return (cls == 0 ? (uint64_t)w : ((uint64_t)w << 21)) | (1ull << 42);
 }
 
+// The same three sums of a node of at most kPack32MaxRows rows in ONE u32: w class0 in bits
+// 0-11, w class1 in bits 12-23, rows in bits 24-31 (the wave tier's fused node kernel: half
+// the LDS, 32-bit LDS atomics and scans).  A row weighs less than 2^kRowWeightBits (its field
+// of the packed row word; Poisson bootstrap weights stop at kPoisTable), so no sum over such
+// a node -- a bin, a cumulative bin or the node total -- leaves its field.
+constexpr int kRowWeightBits = 4;
+constexpr int kPack32MaxRows = 255;
+constexpr int kPack32MaxWeight = 1 << kRowWeightBits;
+constexpr uint32_t kPack32Mask12 = (1u << 12) - 1u;
+static_assert(kPoisTable < kPack32MaxWeight, "a bootstrap weight must fit the row word's weight field");
+static_assert(kPack32MaxWeight * kPack32MaxRows < 4096, "a 255-row node's class weight must fit 12 bits");
+static_assert(kPack32MaxRows < 256, "a 255-row node's row count must fit 8 bits");
+DML_HD uint32_t pack_bin32(int cls, uint32_t w) { return (cls == 0 ? w : (w << 12)) | (1u << 24); }
+DML_HD uint32_t bin32_w0(uint32_t v) { return v & kPack32Mask12; }
+DML_HD uint32_t bin32_w1(uint32_t v) { return (v >> 12) & kPack32Mask12; }
+DML_HD uint32_t bin32_rows(uint32_t v) { return v >> 24; }
+
+// fields of a packed binary histogram word of either width (CT: the u64 word or the u32 one)
+template <class CT>
+DML_HD uint32_t pk_w0(CT v) {
+  if constexpr (sizeof(CT) == 8) return (uint32_t)((uint64_t)v & kPackMask21);
+  else return bin32_w0((uint32_t)v);
+}
+template <class CT>
+DML_HD uint32_t pk_w1(CT v) {
+  if constexpr (sizeof(CT) == 8) return (uint32_t)(((uint64_t)v >> 21) & kPackMask21);
+  else return bin32_w1((uint32_t)v);
+}
+template <class CT>
+DML_HD uint32_t pk_rows(CT v) {
+  if constexpr (sizeof(CT) == 8) return (uint32_t)((uint64_t)v >> 42);
+  else return bin32_rows((uint32_t)v);
+}
+
 // ---- impurity from channel sums ----------------------------------------------------
 #if defined(__HIPCC__)
 #pragma clang fp contract(off)

@@ -448,6 +448,16 @@ void dml_reg_exponents(const int64_t* cnt, int64_t targets, int32_t* out) {
   out[0] = e1; out[1] = e2;
 }
 
+// the wave tier's narrow histogram word (forest_common.h pack_bin32), for host tests of the
+// text the HIP kernels compile: the word of one row, and a word's {w0, w1, rows} fields
+uint32_t dml_pack_bin32(int32_t cls, uint32_t w) { return pack_bin32(cls, w); }
+void dml_bin32_fields(uint32_t v, uint32_t* out) {
+  out[0] = bin32_w0(v); out[1] = bin32_w1(v); out[2] = bin32_rows(v);
+  // the width-generic accessors the kernels call must agree with them
+  if (pk_w0<uint32_t>(v) != out[0] || pk_w1<uint32_t>(v) != out[1] || pk_rows<uint32_t>(v) != out[2]) out[2] = ~0u;
+}
+void dml_pack32_limits(int32_t* out) { out[0] = kPack32MaxRows; out[1] = kPack32MaxWeight; out[2] = kPoisTable; }
+
 int64_t dml_cpu_forest_num_nodes(void* h) {
   CpuForest* F = (CpuForest*)h;
   int64_t s = 0;

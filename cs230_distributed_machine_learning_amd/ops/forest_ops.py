@@ -32,7 +32,9 @@ INT32_MAX = 2**31 - 1
 
 @dataclass
 class ForestTiers:
-    """Node-size tiers of the HIP builder (see forest.hip header)."""
+    """Node-size tiers of the HIP builder (see forest.hip header).  Binary classification
+    builds run the wave tier on nodes of 65..255 rows with a 32-bit packed histogram word
+    (``wave_max_arg``, ``kg_wave_bin``); every other build keeps ``wave_max`` / ``kg_wave``."""
 
     sub_max: int = 64          # <= 64 rows: one wave finishes the whole subtree (k_subtree)
     sub_small: int = 32        # subtree roots of <= 32 rows: tier 4, half-size LDS row cache (2x per CU)
@@ -40,6 +42,10 @@ class ForestTiers:
     wave_max: int = 512         # sweeps: profiles/r1_forest_ab_experiments.md, r2_tier_sweep.txt
     # binary classification (2-wave block-tier nodes, forest.hip DML_BLOCK_NT): the block tier
     # takes nodes above 256 rows -- sweep build 0.974 -> 0.960 s (profiles/r6_block_nt128_sweep.txt)
+    # The binary wave tier's fused kernel packs a node's histogram bin into ONE 32-bit word
+    # (forest_common.h pack_bin32: 12/12/8-bit fields), which holds nodes of <= 255 rows: the
+    # build's wave_max argument is clamped to WAVE_MAX_NARROW (wave_max_arg below) and nodes of
+    # exactly 256 rows go to the block tier.  Tier boundaries never change a tree.
     wave_max_bin: int = 256
     block_max: int = 65536      # r5 (block tier at 4 WGs/CU): 65536 vs 32768 -1.7 % sweep build, bench +2.6 %
                                 # (profiles/r5_block_max_sweep.txt; r2 kernels: 32768 beat 131072 by 4 %)
@@ -50,6 +56,11 @@ class ForestTiers:
     # (GBRT config 6: 6.38 -> 7.32 CV-fits/s at 2048, 7.17 at 8192, 7.27 at 1024)
     block_max_all: int = 2048
     kg_wave: int = 4
+    # binary classification: 1 KB of LDS per feature with the 32-bit word (forest.hip clamps the
+    # group to DML_KGMAX_WAVE32, the 64-bit fallback kernel to its own 4).
+    # 5: max_features = 10 runs in two equal rounds at 5.8 KB of LDS per wave -- sweep build
+    # 0.907 s, against 0.911 s at 8 and 0.916 s at 4 (profiles/r7_wave_hist32_sweep.txt)
+    kg_wave_bin: int = 5
     kg_block: int = 16
     kg_large: int = 16
     # regression builds (boosting stages): smaller large-tier row chunks and feature rounds,
@@ -77,6 +88,8 @@ class ForestTiers:
         if n_channels == 3 and not os.environ.get("DML_TIER_WAVE_MAX"):   # binary classification
             t.wave_max = min(t.wave_max, t.wave_max_bin)
         t.kg_wave = max(1, min(t.kg_wave, (24 * 1024) // per_feat, 4))     # k_nodes<64>: KGMAX 4
+        if n_channels == 3 and (os.environ.get("DML_TIER_KG_WAVE_BIN") or not os.environ.get("DML_TIER_KG_WAVE")):
+            t.kg_wave = max(1, min(t.kg_wave_bin, 8))   # the kernel clamps to its DML_KGMAX_WAVE32 (5; A/B builds 8)
         t.kg_block = max(1, min(t.kg_block, (96 * 1024) // per_feat, 16))  # k_nodes<256>: KGMAX 16
         t.kg_large = max(1, min(t.kg_large, (96 * 1024) // per_feat, 64))
         t.kg_large_reg = max(1, min(t.kg_large_reg, (96 * 1024) // per_feat, 64))
@@ -230,12 +243,24 @@ def workspace_bytes(rows_total: int, T: int, d: int, n_classes: int, is_reg: boo
     a = native.ForestArgs()
     a.d, a.n_classes, a.is_reg, a.T = d, (n_classes if not is_reg else 1), int(is_reg), T
     a.rows_total = int(rows_total)
-    a.wave_max, a.block_max, a.chunk = t.wave_max, t.block_max, t.chunk
+    a.wave_max, a.block_max, a.chunk = wave_max_arg(t, is_reg, n_classes), t.block_max, t.chunk
     a.kg_wave, a.kg_block, a.kg_large, a.slack_wave, a.sub_max = t.kg_wave, t.kg_block, t.kg_large, t.slack_wave, t.sub_max
     a.sub_small = t.sub_small
     if _bigsub_on(t, is_reg, n_classes, d, None):   # the smaller tier 1 has more block-tier nodes
         a.wave_max = min(t.wave_max, t.bigsub_max)
     return int(native.hip_lib().dml_forest_workspace_bytes(ctypes.byref(a)))
+
+
+WAVE_MAX_NARROW = 255   # forest_common.h kPack32MaxRows
+
+
+def wave_max_arg(t: "ForestTiers", is_reg: bool, n_classes: int) -> int:
+    """The wave_max a build passes: binary classification stays within the narrow histogram
+    word's 255 rows, so the builder launches the 32-bit wave kernel; an explicit
+    DML_TIER_WAVE_MAX is passed as it is (above 255 the builder keeps the 64-bit kernel)."""
+    if not is_reg and n_classes == 2 and not os.environ.get("DML_TIER_WAVE_MAX"):
+        return min(t.wave_max, WAVE_MAX_NARROW)
+    return t.wave_max
 
 
 def _bigsub_on(t: "ForestTiers", is_reg: bool, n_classes: int, d: int, mono) -> bool:
@@ -542,7 +567,8 @@ def build_gpu(Xb: torch.Tensor, ycls: Optional[torch.Tensor], yreg: Optional[tor
     a.rows_total = int(row_off[-1])
     a.max_active = int(counts.max()) if T else 0
     pool_cap = _pool_bound(counts, specs) + T
-    a.wave_max, a.block_max, a.chunk = tiers.wave_max, tiers.block_max, (tiers.chunk_reg if is_reg else tiers.chunk)
+    a.wave_max, a.block_max, a.chunk = (wave_max_arg(tiers, is_reg, n_classes), tiers.block_max,
+                                        (tiers.chunk_reg if is_reg else tiers.chunk))
     a.kg_wave, a.kg_block, a.slack_wave = tiers.kg_wave, tiers.kg_block, tiers.slack_wave
     if T and os.environ.get("DML_TIER_KG_BLOCK") is None:
         # block tier: feature groups no wider than the batch's largest max_features (a node's
