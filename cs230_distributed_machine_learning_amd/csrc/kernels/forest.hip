@@ -73,6 +73,13 @@ template <int MODE> constexpr int block_nt() { return MODE == 1 ? DML_BLOCK_NT :
 #ifndef DML_KGW_LARGE
 #define DML_KGW_LARGE 32       // k_hist_large: widest round of a row-window node (two 16-B pieces of the line)
 #endif
+#ifndef DML_LARGE_STASH
+// large tier, feature-subset rounds: 1 keeps the 16-B bscr slot per row even when the build has
+// the feature-major table.  0: k_hist_large stores no slot then and k_partition_large reads the
+// split feature's bytes from XbT (n / m bytes per row of an m-row node instead of a 16-B slot
+// written and a 16-B slot fetched for one byte; docs/BIN_STASH.md)
+#define DML_LARGE_STASH 0
+#endif
 #ifndef DML_PART_KEEP
 #define DML_PART_KEEP 2        // block-tier partition: rounds whose row ids pass 1 keeps in registers (0/1/2: 1.018/1.014/1.009 s sweep build, r5 e6)
 #endif
@@ -245,7 +252,7 @@ struct LState {
   int32_t best_feat, best_bin, split, nl;
   double best_gain;
   int32_t best_pos; // visiting position of the best split's feature
-  int32_t scr_n;    // positions [0, scr_n) have their bins in Ctx::bscr (round 0, <= 16 features)
+  int32_t scr_n;    // positions [0, scr_n) have their bins in Ctx::bscr (round 0, <= 16 features; 0: large_stash)
   double best_mid;  // monotonic_cst: middle value of the best split
   // whole-histogram levels (Ctx::full_cur): features [0, scr_id) -- by feature id -- have their
   // bins in bscr; derive: the histogram is parent - sibling (no row pass), par / sib the
@@ -2871,6 +2878,10 @@ __global__ __launch_bounds__(256) void k_bigsub(Ctx c, int set_cur) {
 // ------------------------------------------------------------------------------------
 // large tier
 // ------------------------------------------------------------------------------------
+// feature-subset rounds (not the whole-histogram levels) keep per-row bscr slots only where the
+// partition has no feature-major table to read the split feature from (or DML_LARGE_STASH)
+__device__ __forceinline__ bool large_stash(const Ctx& c) { return DML_LARGE_STASH != 0 || c.XbT == nullptr; }
+
 // one wave per large node: state + the first feature group of its visiting order
 __global__ __launch_bounds__(64) void k_large_prep(Ctx c, int set_cur, int nL) {
   const int slot = blockIdx.x;
@@ -2888,7 +2899,7 @@ __global__ __launch_bounds__(64) void k_large_prep(Ctx c, int set_cur, int nL) {
   st.best_gain = -INFINITY;
   st.best_mid = 0.0;
   st.best_pos = 1 << 30;
-  st.scr_n = st.g <= 16 ? st.g : 0;
+  st.scr_n = (st.g <= 16 && large_stash(c)) ? st.g : 0;
   st.scr_id = 0; st.derive = 0; st.par = -1; st.sib = -1;
   c.lyy[slot] = 0ull;
   if (c.full_cur) {
@@ -2927,6 +2938,9 @@ __global__ __launch_bounds__(256) void k_hist_large(Ctx c, int fround) {
   // node state read once (the loop's bscr stores could alias it: a reference would reload it)
   const int st_pos = fround >= 0 ? fround : __builtin_amdgcn_readfirstlane(st.pos);
   const int64_t st_start = st.on.start;
+  // the launch's first round stores the rows' bscr slots: always at a whole-histogram level
+  // (LState::scr_id), at a feature-subset round only when the partition reads them (large_stash)
+  const bool stash = __builtin_amdgcn_readfirstlane((st_pos == 0 && (fround >= 0 || large_stash(c))) ? 1 : 0) != 0;
   if (st.done || (fround >= 0 && st.derive)) return;
   const int r0 = DML_LCHUNK * c.chunk;
   if (r0 >= st.on.count) return;
@@ -3030,7 +3044,7 @@ __global__ __launch_bounds__(256) void k_hist_large(Ctx c, int fround) {
       };
       auto consume = [&](int r, bool valid, const uint32_t* b, const PRaw& pr) {
         if (!valid) return;
-        if (st_pos == 0) {   // round 0: bins of visiting positions 0..15 (Ctx::bscr)
+        if (stash) {   // round 0: bins of visiting positions 0..15 (Ctx::bscr); wave-uniform
           uint32_t w4[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
           for (int j = 0; j < G && j < 16; ++j) w4[j >> 2] |= (j < g ? b[j] & 0xFFu : 0u) << (8 * (j & 3));
@@ -3432,14 +3446,13 @@ __global__ __launch_bounds__(256) void k_partition_large(Ctx c) {
   // split bin at row position p: from the histogram pass's scratch if the final round's
   // group produced the best split (st.best_j >= 0), else gathered from the table -- its
   // feature-major copy when present (a node's rows are sorted: lanes read neighbouring bytes
-  // of one feature line instead of one row line each)
+  // of one feature line instead of one row line each; the loop of its own below)
   const int bj = st.scr_id > 0 ? (st.best_feat < st.scr_id ? st.best_feat : -1)
                                : (st.best_pos < st.scr_n ? st.best_pos : -1);
   const uint8_t* xfeat = c.XbT ? c.XbT + (int64_t)feat * c.n : nullptr;
   auto bin_of = [&](int p, uint32_t row) -> int {
     if (row == INV) return 0;
     if (bj >= 0) return (int)c.bscr[(st.on.start + p) * 16 + bj];
-    if (xfeat) return (int)xfeat[row & c.rmask];
     return (int)c.Xb[(int64_t)(row & c.rmask) * c.ld + feat];
   };
   // regression: sum w y2q of the left rows (k_large_finish completes the left child's sums),
@@ -3451,7 +3464,42 @@ __global__ __launch_bounds__(256) void k_partition_large(Ctx c) {
   auto y_of = [&](uint32_t row) -> float { return ty ? ty[(row != INV ? row : 0u) & c.rmask] : 0.0f; };
   unsigned long long lyy = 0ull;
   int myL = 0;
-  {
+  auto rank = [&](int t0, bool left, uint32_t wd, float y) {
+    const uint64_t ml = __ballot(left);
+    if (lane == 0) lflag[(t0 - r0) / 64 + wid] = ml;
+    myL += left ? 1 : 0;
+    if (ty && left) {
+      int64_t yq, y2q;
+      reg_quantize(y, c.rq, yq, y2q);
+      lyy += (unsigned long long)((int64_t)word_weight(c, s, wd) * y2q);
+    }
+  };
+  if (bj < 0 && xfeat) {
+    // no slot holds the split feature (every node of a feature-subset level when the build has
+    // XbT: large_stash): its bytes come from the feature-major line.  Straight-line steps -- row
+    // positions clamped into the chunk (a position past r1 re-reads the last row and is masked
+    // by its index, no select on a loaded id), no load under a mask: 41 instead of 45 ms over
+    // the sweep build's two builds against the loop below.  The bytes run one step ahead of the
+    // ranking and the row ids one step ahead of the bytes; two and three steps each measured
+    // the same (docs/BIN_STASH.md)
+    auto pass1 = [&](auto REGc) __attribute__((always_inline)) {
+      constexpr bool REG = decltype(REGc)::value;
+      auto rid = [&](int r) -> uint32_t { return rows[min(r, r1 - 1)]; };
+      auto yv = [&](uint32_t wd) -> float { return REG ? ty[wd & c.rmask] : 0.0f; };
+      uint32_t ra = rid(r0 + tid), rbn = rid(r0 + tid + 256);
+      int ba = (int)xfeat[ra & c.rmask];
+      float ya = yv(ra);
+      for (int t0 = r0; t0 < r1; t0 += 256) {
+        const int bb = (int)xfeat[rbn & c.rmask];
+        const float yb = yv(rbn);
+        const uint32_t rc2 = rid(t0 + 512 + tid);
+        rank(t0, t0 + tid < r1 && ba <= bin, ra, ya);
+        ra = rbn; ba = bb; ya = yb; rbn = rc2;
+      }
+    };
+    if (ty) pass1(std::true_type{});
+    else pass1(std::false_type{});
+  } else {
     uint32_t ra = row_at(r0 + tid);
     int ba = bin_of(r0 + tid, ra);
     float ya = y_of(ra);
@@ -3460,15 +3508,7 @@ __global__ __launch_bounds__(256) void k_partition_large(Ctx c) {
       const int bb = bin_of(t0 + 256 + tid, rbn);
       const float yb = y_of(rbn);
       const uint32_t rc2 = row_at(t0 + 512 + tid);
-      const bool left = ra != INV && ba <= bin;
-      const uint64_t ml = __ballot(left);
-      if (lane == 0) lflag[(t0 - r0) / 64 + wid] = ml;
-      myL += left ? 1 : 0;
-      if (ty && left) {
-        int64_t yq, y2q;
-        reg_quantize(ya, c.rq, yq, y2q);
-        lyy += (unsigned long long)((int64_t)word_weight(c, s, ra) * y2q);
-      }
+      rank(t0, ra != INV && ba <= bin, ra, ya);
       ra = rbn; ba = bb; ya = yb; rbn = rc2;
     }
   }
@@ -4118,6 +4158,8 @@ const char* dml_forest_last_error(int* line) {
 
 // 1: binary builds with wave_max <= 255 run the narrow-word wave kernel (DML_WAVE_HIST32)
 int dml_forest_wave_hist32() { return DML_WAVE_HIST32 != 0 ? 1 : 0; }
+// 1: the large tier keeps per-row bscr slots in builds that have XbT too (DML_LARGE_STASH)
+int dml_forest_large_stash() { return DML_LARGE_STASH != 0 ? 1 : 0; }
 int dml_forest_sizeof_treespec() { return (int)sizeof(TreeSpec); }
 int dml_forest_sizeof_args() { return (int)sizeof(ForestArgs); }
 int dml_forest_sizeof_node() { return (int)sizeof(NodeRec); }
