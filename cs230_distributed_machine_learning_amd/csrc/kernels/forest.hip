@@ -80,6 +80,20 @@ template <int MODE> constexpr int block_nt() { return MODE == 1 ? DML_BLOCK_NT :
 // written and a 16-B slot fetched for one byte; docs/BIN_STASH.md)
 #define DML_LARGE_STASH 0
 #endif
+#ifndef DML_BLOCK_STASH_PLANES
+// block tier (every NT > 64 node kernel): 1 keeps the first feature group's bins of a node as
+// ceil(g / 4) dword planes inside the node's own bscr range (forest_common.h stash_plane_base):
+// 4 ceil(g / 4) bytes stored per row by the histogram pass and ONE coalesced dword read per row
+// by the partition, instead of a 16-B slot stored and a 16-B slot fetched for one byte.
+// 0: the 16-B slots (A/B builds; docs/BLOCK_STASH.md)
+#define DML_BLOCK_STASH_PLANES 1
+#endif
+#ifndef DML_BLOCK_PART_ALL
+// block tier: 1 takes the two-pass partition for every node whose flags fit the dead histogram
+// LDS (the group-offset scan walks ceil(ngrp / NT) groups per thread), 0 only for nodes of
+// <= 128 NT rows, two groups per thread (docs/BLOCK_STASH.md, part 2)
+#define DML_BLOCK_PART_ALL 1
+#endif
 #ifndef DML_PART_KEEP
 #define DML_PART_KEEP 2        // block-tier partition: rounds whose row ids pass 1 keeps in registers (0/1/2: 1.018/1.014/1.009 s sweep build, r5 e6)
 #endif
@@ -1242,6 +1256,13 @@ __device__ __forceinline__ void hist_add(CT* hj, const Ctx& c, int b, const PL& 
   }
 }
 
+// block-tier dword-plane stash (DML_BLOCK_STASH_PLANES): word p of a plane.  The plane's base is
+// wave-uniform (scalar registers) and the lane's part is ONE 32-bit byte offset (4 p < 2^32: a
+// node has at most kPackMaxRows rows) -- the register the 16-B slot's address needed
+__device__ __forceinline__ uint32_t* plane_word(uint8_t* plane, int p) {
+  return (uint32_t*)(plane + 4u * (uint32_t)p);
+}
+
 // H32 (wave tier of a binary build whose wave_max <= kPack32MaxRows): the narrow u32 word
 template <int NT, int MODE, int FC, bool H32 = false>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? DML_NODES_WPE_REG : (MODE == 0 ? DML_NODES_WPE_MC : (NT == 64 ? DML_NODES_WPE_WAVE : DML_NODES_WPE)), (MODE == 1 && NT == 64) ? DML_NODES_WPE_WAVE_MAX : 8))) void k_nodes(Ctx c, int tier, int set_cur,
@@ -1291,6 +1312,11 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
   const uint32_t* rows = c.rows_cur + on.start;
   const float* ty = tree_y(c, s);
   const int cnt = on.count;
+  // block tier: the first group's bins go to dword planes inside the node's bscr range, plane w
+  // at stash0 + 4 cnt w (wave-uniform: start and cnt are the node's), not to 16-B slots per row
+  constexpr bool PLANES = NT > 64 && DML_BLOCK_STASH_PLANES != 0;
+  uint8_t* const stash0 = c.bscr + stash_plane_base(on.start, cnt, 0);
+  auto plane = [&](int w) -> uint8_t* { return stash0 + 4 * (int64_t)cnt * w; };
   // rows (+ bootstrap weight + label payload) of a <= NT*RPT-row node stay in registers
   // for every feature group and the partition; larger nodes stream in NT*RPT chunks.
   // (block tier, DML_BLOCK_STREAM_ONLY: nodes there have > wave_max >= NT rows, so the
@@ -1453,7 +1479,14 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
             uint32_t w4[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
             for (int j = 0; j < G && j < 16; ++j) w4[j >> 2] |= (j < g ? b[j] & 0xFFu : 0u) << (8 * (j & 3));
-            *(uint4*)(c.bscr + (on.start + base + tid) * 16) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
+            if constexpr (PLANES) {
+              // ceil(G / 4) >= ceil(g / 4) coalesced dword stores (a plane past the group's last
+              // holds zeros inside the node's own range; an unconditional count keeps vmcnt exact)
+#pragma unroll
+              for (int w = 0; w < stash_planes(G); ++w) *plane_word(plane(w), base + tid) = w4[w];
+            } else {
+              *(uint4*)(c.bscr + (on.start + base + tid) * 16) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
+            }
           }
           if (valid) {
             const PL pl = payload_finish<MODE, PK, PL>(c, s, ty, pr);
@@ -1517,10 +1550,17 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
           for (int j = 0; j < G; ++j) b[j >> 2] |= (j < g ? (w[fdw[j]] >> fsh[j]) & 0xFFu : 0u) << (8 * (j & 3));
         };
         auto consume = [&](int base, bool valid, const uint32_t* b, const PRaw& pr) {
-          if (NT > 64 && pos == 0 && valid)
-            *(uint4*)(c.bscr + (on.start + base + tid) * 16) =
-                make_uint4(b[0], NPK > 1 ? b[NPK > 1 ? 1 : 0] : 0u, NPK > 2 ? b[NPK > 2 ? 2 : 0] : 0u,
-                           NPK > 3 ? b[NPK > 3 ? 3 : 0] : 0u);
+          if (NT > 64 && pos == 0 && valid) {
+            if constexpr (PLANES) {
+              // b[] IS the planes' content: one coalesced dword store per packed register
+#pragma unroll
+              for (int w = 0; w < stash_planes(G); ++w) *plane_word(plane(w), base + tid) = b[w];
+            } else {
+              *(uint4*)(c.bscr + (on.start + base + tid) * 16) =
+                  make_uint4(b[0], NPK > 1 ? b[NPK > 1 ? 1 : 0] : 0u, NPK > 2 ? b[NPK > 2 ? 2 : 0] : 0u,
+                             NPK > 3 ? b[NPK > 3 ? 3 : 0] : 0u);
+            }
+          }
           if (valid) {
             const PL pl = payload_finish<MODE, PK, PL>(c, s, ty, pr);
 #pragma unroll
@@ -1605,7 +1645,13 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
 #pragma unroll
             for (int j = 0; j < KGMAX && j < 16; ++j)
               if (j < g) w4[j >> 2] |= (bins[j][u] & 0xFFu) << (8 * (j & 3));
-            *(uint4*)(c.bscr + (on.start + base + tid + NT * u) * 16) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
+            if constexpr (PLANES) {
+#pragma unroll
+              for (int w = 0; w < stash_planes(KGMAX); ++w)
+                if (4 * w < g) *plane_word(plane(w), base + tid + NT * u) = w4[w];
+            } else {
+              *(uint4*)(c.bscr + (on.start + base + tid + NT * u) * 16) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
+            }
           }
       }
       if (NT == 64 && !reg_rows && pos < 16) {
@@ -1677,8 +1723,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
           sc->best_mid = rmid[jj];
         }
         sc->best_j = upd ? jj : -1;
-        // bscr slots: byte q of a row's 16-B slot = visiting position q (written by the
-        // streamed histogram passes: the block tier's first group, the wave tier's groups)
+        // bscr: visiting position q of a row is byte q of its 16-B slot (wave tier's groups) or
+        // byte q & 3 of its word of plane q >> 2 (block tier's first group, PLANES) -- written
+        // by the streamed histogram passes
         if (!reg_rows) sc->scr_n = NT > 64 ? (pos == 0 ? min(g, 16) : sc->scr_n) : min(16, pos + g);
         sc->nonconst = min(nc0 + __popcll(m), k);
         sc->pos = pos + g;
@@ -1746,7 +1793,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
 #ifdef DML_X2_PART   // sensitivity build: the (idempotent) partition pass runs twice
   for (int rep_ = 0; rep_ < 2; ++rep_) {
 #endif
-  if (NT > 64 && !reg_rows && cnt <= 128 * NT && (size_t)((cnt + 63) / 64) * 12 <= (size_t)KG * span * sizeof(CT)) {
+  if (NT > 64 && !reg_rows && (DML_BLOCK_PART_ALL || cnt <= 128 * NT) &&
+      (size_t)((cnt + 63) / 64) * 12 <= (size_t)KG * span * sizeof(CT)) {
     // block tier, streamed node: two passes and two barriers for the whole node (not two per
     // chunk).  Pass 1 ranks every row (split bin from the histogram pass's scratch, else
     // gathered) into one ballot word per 64-row group in LDS (the histograms are dead);
@@ -1757,6 +1805,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
     const int ngrp = (cnt + 63) / 64;
     const int bjs = __builtin_amdgcn_readfirstlane((sc->best_pos < sc->scr_n) ? sc->best_pos : -1);
     const int fsplit = __builtin_amdgcn_readfirstlane(feat), bsplit = __builtin_amdgcn_readfirstlane(bin);
+    // PLANES: the split position's plane (wave-uniform base) and its byte's shift in the word
+    uint8_t* const bpl = plane(max(bjs, 0) >> 2);
+    const int bsh = 8 * (max(bjs, 0) & 3);
     constexpr int U = 4;   // positions per thread per round, all loads issued before the ballots
     // the row ids of the first KR rounds are loaded WITH the split bins and kept in registers
     // for pass 2 (which then issues no loads for them): one memory round trip less per round
@@ -1775,7 +1826,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
         const int p = min(p0 + u * NT + tid, cnt - 1);
         const uint32_t r = (KR > 0 || bjs < 0) ? rows[p] : 0u;
         if (bjs >= 0) {
-          bv[u] = c.bscr[(on.start + p) * 16 + bjs];
+          if constexpr (PLANES) bv[u] = (*plane_word(bpl, p) >> bsh) & 0xFFu;   // one coalesced dword per lane
+          else bv[u] = c.bscr[(on.start + p) * 16 + bjs];
         } else {
           bv[u] = c.Xb[(int64_t)(r & c.rmask) * c.ld + fsplit];
         }
@@ -1791,8 +1843,23 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
       }
     }
     __syncthreads();
-    // exclusive prefix of the groups' left counts (<= 2 NT groups: two per thread)
-    {
+    // exclusive prefix of the groups' left counts: thread t owns groups [gpt t, gpt (t + 1)),
+    // gpt = ceil(ngrp / NT) of them (8 at 65 536 rows and 128 threads), so no group of a node
+    // whose flags fit the LDS is left unranked whatever block_max is
+    if constexpr (DML_BLOCK_PART_ALL) {
+      const int gpt = (ngrp + NT - 1) / NT, gb = gpt * tid;
+      int tot = 0;
+      for (int i = 0; i < gpt; ++i) tot += gb + i < ngrp ? __popcll(lflag[gb + i]) : 0;
+      const int incl = wave::incl_scan<int>(tot);
+      if (lane == 63) sc->wcnt[wid] = incl;
+      __syncthreads();
+      int ex = incl - tot;
+      for (int w = 0; w < wid; ++w) ex += sc->wcnt[w];
+      for (int i = 0; i < gpt && gb + i < ngrp; ++i) {
+        loff[gb + i] = ex;
+        ex += __popcll(lflag[gb + i]);
+      }
+    } else {   // <= 2 NT groups: two per thread
       const int g0 = 2 * tid, g1 = 2 * tid + 1;
       const int c0 = g0 < ngrp ? __popcll(lflag[g0]) : 0, c1 = g1 < ngrp ? __popcll(lflag[g1]) : 0;
       const int incl = wave::incl_scan<int>(c0 + c1);
@@ -1845,7 +1912,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
   const int bj_scr = (!reg_rows && sc->best_pos < sc->scr_n) ? sc->best_pos : -1;
   auto pbin = [&](int p, uint32_t r) -> uint32_t {
     if (r == INVR) return 0u;
-    if (bj_scr >= 0) return (uint32_t)c.bscr[(on.start + p) * 16 + bj_scr];
+    if (bj_scr >= 0) {
+      if constexpr (PLANES) return (*plane_word(plane(bj_scr >> 2), p) >> (8 * (bj_scr & 3))) & 0xFFu;
+      else return (uint32_t)c.bscr[(on.start + p) * 16 + bj_scr];
+    }
     return (uint32_t)c.Xb[(int64_t)(r & c.rmask) * c.ld + feat];
   };
   uint32_t nrow = INVR, nbin = 0, frow = INVR;
@@ -1864,7 +1934,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
 #pragma unroll
         for (int u = 0; u < RPT; ++u)
           rbin[u] = rrow[u] == 0xFFFFFFFFu ? 0u
-                  : bj_scr >= 0 ? (uint32_t)c.bscr[(on.start + cb + tid + NT * u) * 16 + bj_scr]
+                  : bj_scr >= 0 ? pbin(cb + tid + NT * u, rrow[u])
                                 : (uint32_t)c.Xb[(int64_t)(rrow[u] & c.rmask) * c.ld + feat];
       }
     }
@@ -4160,6 +4230,8 @@ const char* dml_forest_last_error(int* line) {
 int dml_forest_wave_hist32() { return DML_WAVE_HIST32 != 0 ? 1 : 0; }
 // 1: the large tier keeps per-row bscr slots in builds that have XbT too (DML_LARGE_STASH)
 int dml_forest_large_stash() { return DML_LARGE_STASH != 0 ? 1 : 0; }
+// 1: the block tier stashes its first group's bins as dword planes (DML_BLOCK_STASH_PLANES)
+int dml_forest_block_stash_planes() { return DML_BLOCK_STASH_PLANES != 0 ? 1 : 0; }
 int dml_forest_sizeof_treespec() { return (int)sizeof(TreeSpec); }
 int dml_forest_sizeof_args() { return (int)sizeof(ForestArgs); }
 int dml_forest_sizeof_node() { return (int)sizeof(NodeRec); }

@@ -209,6 +209,21 @@ DML_HD uint32_t pk_rows(CT v) {
   else return bin32_rows((uint32_t)v);
 }
 
+// ---- block tier: first-group bin stash as dword planes ------------------------------
+// A block-tier node owns bytes [16 start, 16 (start + cnt)) of the per-row bin scratch.  The
+// bins of its first feature group (visiting positions q < g <= 16) of row position p live in
+// ceil(g / 4) planes of one 32-bit word per row position: plane w = q >> 2 starts at byte
+// 16 start + 4 cnt w, word p of it carries positions 4w .. 4w+3 of row p, position q in byte
+// q & 3 (little endian: bits 8 (q & 3) ..).  The histogram pass stores ceil(g / 4) coalesced
+// dwords per row and the partition reads ONE (its split position's plane) instead of a 16-B
+// slot written and a 16-B slot fetched for one byte.  Four planes fill the range exactly.
+constexpr int kStashSlot = 16;   // scratch bytes per row position, either layout
+DML_HD constexpr int stash_planes(int g) { return ((g < kStashSlot ? g : kStashSlot) + 3) >> 2; }
+DML_HD int64_t stash_plane_base(int64_t start, int cnt, int w) { return kStashSlot * start + 4 * (int64_t)cnt * w; }
+DML_HD int64_t stash_plane_byte(int64_t start, int cnt, int p, int q) {
+  return stash_plane_base(start, cnt, q >> 2) + 4 * (int64_t)p + (q & 3);
+}
+
 // ---- impurity from channel sums ----------------------------------------------------
 #if defined(__HIPCC__)
 #pragma clang fp contract(off)

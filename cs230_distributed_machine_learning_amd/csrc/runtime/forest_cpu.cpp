@@ -458,6 +458,17 @@ void dml_bin32_fields(uint32_t v, uint32_t* out) {
 }
 void dml_pack32_limits(int32_t* out) { out[0] = kPack32MaxRows; out[1] = kPack32MaxWeight; out[2] = kPoisTable; }
 
+// the block tier's dword-plane bin stash (forest_common.h stash_plane_*), for host tests of the
+// address arithmetic the HIP kernels compile: the number of planes of a g-position group, a
+// plane's first byte, and the byte of every (row position p, visiting position q) of a node,
+// out[p * g + q]
+int32_t dml_stash_planes(int32_t g) { return stash_planes(g); }
+int64_t dml_stash_plane_base(int64_t start, int32_t cnt, int32_t w) { return stash_plane_base(start, cnt, w); }
+void dml_stash_plane_bytes(int64_t start, int32_t cnt, int32_t g, int64_t* out) {
+  for (int32_t p = 0; p < cnt; ++p)
+    for (int32_t q = 0; q < g; ++q) out[(int64_t)p * g + q] = stash_plane_byte(start, cnt, p, q);
+}
+
 int64_t dml_cpu_forest_num_nodes(void* h) {
   CpuForest* F = (CpuForest*)h;
   int64_t s = 0;
