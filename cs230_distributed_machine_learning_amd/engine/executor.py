@@ -164,6 +164,7 @@ def run_candidates(data, spec: JobSpec, candidate_ids: Sequence[int]) -> List[Ca
     if scoring_mod.needs_proba(scorer):   # families that only predict labels by default add probabilities
         for t in tasks:
             t.need_proba = True
+            t.scorer = scorer
     if data.is_gpu and not getattr(fam, "uses_forest_arena", False):
         from ..ops import forest_ops
 

@@ -147,8 +147,9 @@ class Predictor:
 
     * ``predict(X)`` -- labels (classifiers, in the dataset's original label values) or values;
     * ``predict_proba(X)`` -- classifiers whose sklearn counterpart has it (forest, logistic,
-      gradient boosting, k-NN); SVC has ``decision_function`` only (sklearn's default
-      ``probability=False``);
+      gradient boosting, k-NN, and an SVC fitted with ``probability=True``: Platt scaling +
+      pairwise coupling, models/svm.py ``svm_proba_numpy``); an SVC fitted with sklearn's
+      default ``probability=False`` has ``decision_function`` only;
     * ``score(X, y)`` -- accuracy (classifiers), R^2 (regressors), mean log-likelihood (PCA),
       the default ``score`` of the sklearn estimator and what a job reports as
       ``accuracy`` / ``r2_score`` / ``score``;
@@ -253,6 +254,11 @@ class Predictor:
             _, proba = vote(finish_distance(acc, metric, p), ytr[idx], k, m["weights"], int(m.get("n_classes", 1)),
                             True)
             return proba.numpy()
+        if kind == "svm":
+            from ..models.svm import svm_has_proba, svm_proba_numpy
+
+            if svm_has_proba(self.model):   # fitted with probability=True: probA / probB per machine
+                return svm_proba_numpy(self.model, X)
         raise AttributeError(f"{self.model_type} has no predict_proba (sklearn's default probability=False)")
 
     # ---- transformers ------------------------------------------------------------------

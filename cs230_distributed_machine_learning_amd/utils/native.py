@@ -149,6 +149,10 @@ def cpu_lib() -> ctypes.CDLL:
             lib.dml_cpu_bin.argtypes = [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64]
             lib.dml_cpu_svm_sizeof_prob.restype = c_i32
             lib.dml_cpu_svm_smo.argtypes = [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]
+            lib.dml_cpu_svm_platt_fit.restype = c_i32
+            lib.dml_cpu_svm_platt_fit.argtypes = [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]
+            lib.dml_cpu_svm_pair_proba.restype = c_i32
+            lib.dml_cpu_svm_pair_proba.argtypes = [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]
             lib.dml_cpu_dp_sizeof_args.restype = c_i32
             lib.dml_cpu_dp_step.restype = c_i32
             lib.dml_cpu_dp_step.argtypes = [c_vp, c_i32]
@@ -218,6 +222,8 @@ def _register_optional(lib) -> None:
                                       c_vp, c_vp, c_vp, c_i64, c_vp, c_i32, c_vp]),
         "dml_svm_split_limits": (c_i32, [c_vp, c_vp, c_vp]),
         "dml_svm_smo": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+        "dml_svm_platt_fit": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
+        "dml_svm_pair_proba": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
         "dml_split_moments": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp]),
         "dml_lr_mfma_tile": (c_i32, []),
         "dml_lr_mfma_fwd": (c_i32, [ctypes.POINTER(LrFwdArgs), c_vp]),

@@ -1,7 +1,10 @@
 """Same search through this engine and through scikit-learn (reference demo_results.py /
 results1.py: "distributed vs non-distributed" wall time and best parameters).
 
-    python examples/compare_sklearn.py [rf|lr|svc|knn|gbrt] [n_rows]
+    python examples/compare_sklearn.py [rf|lr|svc|svc_proba|knn|gbrt] [n_rows]
+
+``svc_proba`` ranks SVC(probability=True) candidates by neg_log_loss (Platt scaling + pairwise
+coupling, docs/SVC_PROBABILITY.md); its scores differ from scikit-learn's by the inner-CV shuffle.
 """
 import os
 import sys
@@ -17,6 +20,7 @@ from cs230_distributed_machine_learning_amd.engine.executor import JobSpec, run_
 from cs230_distributed_machine_learning_amd.search.grid import ParameterGrid  # noqa: E402
 
 which = sys.argv[1] if len(sys.argv) > 1 else "rf"
+scoring = None   # the estimator's default scorer (accuracy)
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 5000
 X, y = make_classification(n, 20, n_informative=8, random_state=0)
 if which == "rf":
@@ -29,6 +33,9 @@ elif which == "lr":
 elif which == "svc":
     from sklearn.svm import SVC as E
     name, grid = "SVC", {"C": [0.3, 1, 3], "kernel": ["rbf", "poly"]}
+elif which == "svc_proba":
+    from sklearn.svm import SVC as E
+    name, grid, scoring = "SVC", {"C": [0.1, 1, 10], "probability": [True], "random_state": [0]}, "neg_log_loss"
 elif which == "knn":
     from sklearn.neighbors import KNeighborsClassifier as E
     name, grid = "KNeighborsClassifier", {"n_neighbors": [3, 7, 15, 31], "weights": ["uniform", "distance"]}
@@ -42,11 +49,11 @@ dev = "cuda:0" if torch.cuda.is_available() else "cpu"
 cands = list(ParameterGrid(grid))
 dd = DeviceData(X, y, True, dev)
 t0 = time.time()
-res = run_candidates(dd, JobSpec(name, cands, cv=5, holdout=False), range(len(cands)))
+res = run_candidates(dd, JobSpec(name, cands, cv=5, holdout=False, scoring=scoring), range(len(cands)))
 t_ours = time.time() - t0
 ours = np.array([r.result["mean_cv_score"] for r in res])
 t0 = time.time()
-ref = GridSearchCV(E(), grid, cv=5, n_jobs=-1).fit(X, y)
+ref = GridSearchCV(E(), grid, cv=5, n_jobs=-1, scoring=scoring).fit(X, y)
 t_sk = time.time() - t0
 sk = ref.cv_results_["mean_test_score"]
 print(f"{name} {len(cands)} candidates x 5 folds on {n}x20 ({dev})")
