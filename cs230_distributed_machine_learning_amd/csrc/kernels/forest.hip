@@ -118,6 +118,15 @@ template <int MODE> constexpr int block_nt() { return MODE == 1 ? DML_BLOCK_NT :
 #ifndef DML_SUB_SEG_REG
 #define DML_SUB_SEG_REG 1     // regression subtrees: segmented evaluation of nodes <= 32 rows
 #endif
+#ifndef DML_SUB_PK16
+// subtree tier (k_subtree, k_bigsub's small nodes), binary classification without monotonic_cst:
+// 1 sorts TWO features per pass with 16-bit keys (forest_common.h pk16_key, wave_ops.h
+// bitonic64_pk16) -- two visiting positions per sort in the one-feature path, 2 * 64 / WD per
+// pass in the segmented path; sums, scores and tie-breaks are the same integers and doubles.
+// 0: one 32-bit key per lane; 2: two per sort in the one-feature path only (A/B builds;
+// docs/SUBTREE_PK16.md)
+#define DML_SUB_PK16 1
+#endif
 #ifndef DML_KGMAX_WAVE
 #define DML_KGMAX_WAVE 4
 #endif
@@ -2123,6 +2132,61 @@ __device__ __forceinline__ void sub_eval(const Ctx& c, const NodeSpec& s, uint64
   bin = bl < 64 ? bsel : -1;
 }
 
+// ---- two features per sort (DML_SUB_PK16): binary classification, no monotonic_cst ---
+// The rows' 16-bit keys of two visiting positions (forest_common.h pk16_key) share a register:
+// the first position in bits 0-15, the second (all absent if there is none) in bits 16-31.
+__device__ __forceinline__ uint32_t sub_sort_pk2(uint64_t mask, int lane, int bin0, int bin1, bool has2, int my_cls, float my_w) {
+  const bool act = (mask >> lane) & 1ull;
+  const uint32_t k0 = act ? pk16_key(bin0, my_cls, (uint32_t)my_w) : kPk16Absent;
+  const uint32_t k1 = (act && has2) ? pk16_key(bin1, my_cls, (uint32_t)my_w) : kPk16Absent;
+  return wave::bitonic64_pk16(k0 | (k1 << 16), lane);
+}
+
+// sub_eval after the sort, for one feature whose sorted 16-bit keys lie one per lane (lanes
+// >= cnt hold absent rows): the same candidates, integer sums, doubles and lowest-bin tie-break
+__device__ __forceinline__ void sub_post_pk(const Ctx& c, const NodeSpec& s, int cnt, int lane, uint32_t sk, double& gain,
+                                            int& bin, bool& nonconst, const double* cw) {
+  const bool valid_row = lane < cnt;
+  const int b = valid_row ? pk16_bin(sk) : 1024;
+  const int bnext = wave::shift_down1<int>(b, lane, 1024);
+  const int blast = wave::bcast<int>(b, cnt - 1);
+  const int bfirst = wave::bcast<int>(b, 0);
+  nonconst = bfirst != blast;
+  const int lrows = lane + 1, rrows = cnt - lrows;
+  const bool cand = valid_row && lane < cnt - 1 && b != bnext && lrows >= s.min_samples_leaf &&
+                    rrows >= s.min_samples_leaf;
+  const uint32_t w = valid_row ? pk16_w(sk) : 0u;
+  ClsAcc L, R;
+  L.init(s.criterion); R.init(s.criterion);
+  const uint32_t pre = wave::incl_scan<uint32_t>(pk16_scan_word(pk16_cls(sk), w));
+  const uint32_t tot = wave::bcast<uint32_t>(pre, cnt - 1);
+  const uint32_t p1 = pre >> 16, p0 = (pre & 0xFFFFu) - p1, q1 = tot >> 16, q0 = (tot & 0xFFFFu) - q1;
+  const double lw0 = (double)p0 * cwk(cw, 0), tw0 = (double)q0 * cwk(cw, 0);
+  const double lw1 = (double)p1 * cwk(cw, 1), tw1 = (double)q1 * cwk(cw, 1);
+  L.add(lw0); R.add(tw0 - lw0);
+  L.add(lw1); R.add(tw1 - lw1);
+  const bool ok = cand && !side_too_light(s, L.w, R.w);
+  double g = -INFINITY;
+  if (ok) g = cls_proxy(L, R, s.criterion);
+  int bl;
+  if (s.criterion == kGini) {   // positive doubles order like their bit patterns (see sub_eval)
+    const uint64_t gb = ok ? __builtin_bit_cast(uint64_t, g) : 0ull;
+    uint64_t mx = gb;
+#define DML_MAXU64_STEP(M) { const uint64_t o = wave::shfl_xor<M>(mx, lane); mx = o > mx ? o : mx; }
+    DML_MAXU64_STEP(32) DML_MAXU64_STEP(16) DML_MAXU64_STEP(8) DML_MAXU64_STEP(4) DML_MAXU64_STEP(2) DML_MAXU64_STEP(1)
+#undef DML_MAXU64_STEP
+    const uint64_t hit = __ballot(ok && gb == mx);
+    bl = hit ? (int)__builtin_ctzll(hit) : 64;
+    g = hit ? __builtin_bit_cast(double, mx) : -INFINITY;
+  } else {
+    bl = ok ? lane : 64;
+    wave::argmax(g, bl, lane);
+  }
+  gain = g;
+  const int bsel = wave::bcast<int>(b, bl & 63);
+  bin = bl < 64 ? bsel : -1;
+}
+
 // ---- segmented evaluation of small subtree nodes (classification) -------------------
 // A node with cnt <= WD rows (WD = 8/16/32) is evaluated on 64 / WD features at once: the
 // wave is cut into WD-lane segments, each segment holds the node's rows compacted into
@@ -2308,6 +2372,124 @@ __device__ __forceinline__ void sub_node_seg(const Ctx& c, const NodeSpec& s, co
   }
 }
 
+// ---- segmented evaluation, two features per segment (DML_SUB_PK16) -------------------
+// bitonic_seg's network on two independent 16-bit keys per lane (wave_ops.h bitonic64_pk16)
+template <int WD>
+__device__ __forceinline__ uint32_t bitonic_seg_pk16(uint32_t key, int lane) {
+  static_assert(WD == 8 || WD == 16 || WD == 32, "segments of 8, 16 or 32 lanes");
+  return wave::bitonic_pk16<WD>(key, lane);
+}
+
+// sub_node_seg's pass after the sort for the S features at visiting positions pos .. pos + S - 1,
+// segment q's sorted 16-bit keys in its first cnt lanes: binary classification's candidates,
+// sums, scores and the selection in visiting order, as in sub_node_seg
+template <int WD>
+__device__ __forceinline__ void seg_post_pk(const Ctx& c, const NodeSpec& s, const FeatPerm& fp, int cnt, int lane, uint32_t sk,
+                                            int pos, int& nonconst, double& best_g, int& best_f, int& best_b,
+                                            const double* cw) {
+  constexpr int S = 64 / WD;
+  const int d = c.d;
+  const int seg = lane / WD, j = lane & (WD - 1);
+  const bool valid_row = j < cnt;
+  const int b = valid_row ? pk16_bin(sk) : 1024;
+  const int bnext = wave::shift_down1<int>(b, lane, 1024);
+  const uint32_t w = valid_row ? pk16_w(sk) : 0u;
+  const bool cand = valid_row && j < cnt - 1 && b != bnext && j + 1 >= s.min_samples_leaf &&
+                    cnt - j - 1 >= s.min_samples_leaf;
+  const bool ncl = valid_row && j < cnt - 1 && b != bnext;
+  double g = -INFINITY;
+  ClsAcc L, R;
+  L.init(s.criterion); R.init(s.criterion);
+  // segment-relative inclusive prefix of the packed (all weight | class-1 weight << 16) words
+  uint32_t pre = wave::incl_scan<uint32_t>(pk16_scan_word(pk16_cls(sk), w));
+  uint32_t base = 0, tot = 0;
+#pragma unroll
+  for (int q = 0; q < S; ++q) {
+    const uint32_t bq = q ? (uint32_t)__builtin_amdgcn_readlane((int)pre, q * WD - 1) : 0u;
+    const uint32_t eq = (uint32_t)__builtin_amdgcn_readlane((int)pre, q * WD + cnt - 1);
+    if (seg == q) { base = bq; tot = eq - bq; }
+  }
+  pre -= base;
+  const uint32_t l1 = pre >> 16, l0 = (pre & 0xFFFFu) - l1, t1 = tot >> 16, t0 = (tot & 0xFFFFu) - t1;
+  const double lw0 = (double)l0 * cwk(cw, 0), tw0 = (double)t0 * cwk(cw, 0);
+  const double lw1 = (double)l1 * cwk(cw, 1), tw1 = (double)t1 * cwk(cw, 1);
+  L.add(lw0); R.add(tw0 - lw0);
+  L.add(lw1); R.add(tw1 - lw1);
+  if (cand && !side_too_light(s, L.w, R.w)) g = cls_proxy(L, R, s.criterion);
+  const bool ok = g != -INFINITY;
+  int bl = ok ? j : 64;
+  argmax_seg<WD>(g, bl, lane);
+  const int bsel = __shfl(b, seg * WD + (bl & (WD - 1)));
+  const uint64_t ncm = __ballot(ncl);
+  uint32_t ncs = 0;   // bit q: segment q's feature is non-constant (and exists)
+#pragma unroll
+  for (int q = 0; q < S; ++q)
+    if (pos + q < d && ((ncm >> (q * WD)) & ((1ull << WD) - 1ull)) != 0ull) ncs |= 1u << q;
+  const int room = s.max_features - nonconst;
+  const bool counted = ((ncs >> seg) & 1u) && __popc(ncs & ((1u << seg) - 1u)) < room;
+  double gq = (counted && bl < 64) ? g : -INFINITY;
+  int qi = (counted && bl < 64) ? seg : 64;
+  auto step = [&](auto Mc) {
+    constexpr int M = decltype(Mc)::value;
+    const double og = wave::shfl_xor<M>(gq, lane);
+    const int oi = wave::shfl_xor<M>(qi, lane);
+    if (og > gq || (og == gq && oi < qi)) { gq = og; qi = oi; }
+  };
+  if constexpr (WD <= 32) step(std::integral_constant<int, 32>{});
+  if constexpr (WD <= 16) step(std::integral_constant<int, 16>{});
+  if constexpr (WD <= 8) step(std::integral_constant<int, 8>{});
+  nonconst = min(s.max_features, nonconst + __popc(ncs));
+  gq = wave::bcast<double>(gq, 0);
+  qi = wave::bcast<int>(qi, 0);
+  if (qi < 64 && gq > best_g) {
+    best_g = gq;
+    best_f = feature_at(fp, pos + qi, d);
+    best_b = __builtin_amdgcn_readlane(bsel, qi * WD);
+  }
+}
+
+// sub_node_seg for binary classification with 2 S features per pass: segment q's low key half
+// holds visiting position pos + q, its high half position pos + S + q.  One packed sort, then
+// the low halves and the high halves are evaluated like two consecutive passes of
+// sub_node_seg's loop (the high halves only while max_features is not yet filled).
+template <int WD>
+__device__ __forceinline__ void sub_node_seg_pk(const Ctx& c, const NodeSpec& s, const FeatPerm& fp, int cnt, int lane, int src,
+                                                int cls_j, uint32_t w_j, const uint8_t* xc, int dp, int& nonconst,
+                                                double& best_g, int& best_f, int& best_b, const double* cw) {
+  static_assert(WD == 8 || WD == 16 || WD == 32, "segments of 8, 16 or 32 lanes");
+  constexpr int S = 64 / WD;
+  const int d = c.d;
+  const int seg = lane / WD, j = lane & (WD - 1);
+  const bool valid_row = j < cnt;
+  const uint32_t pay = pk16_key(0, cls_j, w_j);
+  // the first 64 visiting positions, one per lane (see sub_node_seg)
+  const int fo = feature_at(fp, min(lane, d - 1), d);
+  for (int pos = 0; nonconst < s.max_features && pos < d; pos += 2 * S) {
+    const bool has_lo = pos + seg < d, has_hi = pos + S + seg < d;
+    int flo = 0, fhi = 0;
+    if (pos + 2 * S <= 64) {
+#pragma unroll
+      for (int q = 0; q < S; ++q) {
+        const int f0 = __builtin_amdgcn_readlane(fo, pos + q), f1 = __builtin_amdgcn_readlane(fo, pos + S + q);
+        if (seg == q) { flo = f0; fhi = f1; }
+      }
+      if (!has_lo) flo = 0;
+      if (!has_hi) fhi = 0;
+    } else {
+      flo = has_lo ? feature_at(fp, pos + seg, d) : 0;
+      fhi = has_hi ? feature_at(fp, pos + S + seg, d) : 0;
+    }
+    const uint32_t bin_lo = (valid_row && has_lo) ? (uint32_t)xc[src * dp + flo] : 0u;
+    const uint32_t bin_hi = (valid_row && has_hi) ? (uint32_t)xc[src * dp + fhi] : 0u;
+    const uint32_t key = valid_row ? (((bin_lo << kPk16BinShift) | pay) | (((bin_hi << kPk16BinShift) | pay) << 16))
+                                   : (kPk16Absent | (kPk16Absent << 16));
+    const uint32_t sk = bitonic_seg_pk16<WD>(key, lane);
+    seg_post_pk<WD>(c, s, fp, cnt, lane, sk & 0xFFFFu, pos, nonconst, best_g, best_f, best_b, cw);
+    if (nonconst < s.max_features && pos + S < d)
+      seg_post_pk<WD>(c, s, fp, cnt, lane, sk >> 16, pos + S, nonconst, best_g, best_f, best_b, cw);
+  }
+}
+
 // Grows the whole subtree under one node of <= 64 rows with ONE wave (k_subtree; k_bigsub
 // for its small nodes): stack[0] / sstats[0..VC) hold the node on entry.  Lane `lane` holds
 // one row of the node: its class / weight / fixed-point target in registers and its bins
@@ -2321,6 +2503,9 @@ __device__ __forceinline__ void subtree_dfs(const Ctx& c, const NodeSpec& s, int
                                             const double* tcw, Alloc alloc PH_ARGS_DECL) {
   const int d = c.d;
   const int VC = c.VC;
+  // two features per sort: binary classification, no monotonic_cst on any node of the build
+  const bool pk16 = !REG && DML_SUB_PK16 != 0 && c.C == 2 && (FC >= 0 || !c.mono);
+  const bool pk16_seg = pk16 && DML_SUB_PK16 != 2;   // 2: the one-feature path only (A/B builds)
   int sp = 1;
   while (sp > 0) {
     --sp;
@@ -2345,12 +2530,26 @@ __device__ __forceinline__ void subtree_dfs(const Ctx& c, const NodeSpec& s, int
       {
         int nc2 = nonconst, bf2 = best_f, bb2 = best_b;
         double bg2 = best_g;
+        if (pk16_seg) {
+          if constexpr (!REG) {
+            if (cnt <= 8) sub_node_seg_pk<8>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nc2, bg2, bf2, bb2, tcw);
+            else if (cnt <= 16) sub_node_seg_pk<16>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nc2, bg2, bf2, bb2, tcw);
+            else sub_node_seg_pk<32>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nc2, bg2, bf2, bb2, tcw);
+          }
+        } else
         if (cnt <= 8) sub_node_seg<8, REG>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nc2, bg2, bf2, bb2, tcw, yq_j);
         else if (cnt <= 16) sub_node_seg<16, REG>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nc2, bg2, bf2, bb2, tcw, yq_j);
         else sub_node_seg<32, REG>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nc2, bg2, bf2, bb2, tcw, yq_j);
         if (bg2 == -12345.0 && bf2 == 7 && nc2 == 3) atomicOr(&c.counters[kOpenOvf], bb2);
       }
 #endif
+      if (pk16_seg) {
+        if constexpr (!REG) {
+          if (cnt <= 8) sub_node_seg_pk<8>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nonconst, best_g, best_f, best_b, tcw);
+          else if (cnt <= 16) sub_node_seg_pk<16>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nonconst, best_g, best_f, best_b, tcw);
+          else sub_node_seg_pk<32>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nonconst, best_g, best_f, best_b, tcw);
+        }
+      } else
       if (cnt <= 8) sub_node_seg<8, REG>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nonconst, best_g, best_f, best_b, tcw, yq_j);
       else if (cnt <= 16) sub_node_seg<16, REG>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nonconst, best_g, best_f, best_b, tcw, yq_j);
       else sub_node_seg<32, REG>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nonconst, best_g, best_f, best_b, tcw, yq_j);
@@ -2358,6 +2557,41 @@ __device__ __forceinline__ void subtree_dfs(const Ctx& c, const NodeSpec& s, int
       PH(1)
       PH_CNT(4, 1)
       PH_CNT(5, cnt)
+    } else if (pk16) {
+      // visiting positions pos and pos + 1 in one sort; the second counts only if the first left
+      // room in max_features, and wins only with a strictly greater score: the sequential outcome
+      if constexpr (!REG)
+      for (int pos = 0; nonconst < s.max_features && pos < d; pos += 2) {
+        const bool has2 = pos + 1 < d;
+        const int f0 = feature_at(fp, pos, d), f1 = has2 ? feature_at(fp, pos + 1, d) : f0;
+        const int bin0 = cache ? xc[my_lr * dp + f0] : (lane < cnt0 ? xg[f0] : 0);
+        const int bin1 = cache ? xc[my_lr * dp + f1] : (lane < cnt0 ? xg[f1] : 0);
+        double g;
+        int bb;
+        bool nc;
+#if defined(DML_X2_SUB) && DML_X2_SUB != 1   // sensitivity: every two-feature evaluation twice
+        {
+          const uint32_t sk2 = sub_sort_pk2(e.mask, lane, bin1, bin0, has2, my_cls, my_w);
+          sub_post_pk(c, s, cnt, lane, sk2 & 0xFFFFu, g, bb, nc, tcw);
+          if (g == -12345.0 && bb == 7) atomicOr(&c.counters[kOpenOvf], (int)nc);
+          sub_post_pk(c, s, cnt, lane, sk2 >> 16, g, bb, nc, tcw);
+          if (g == -12345.0 && bb == 7) atomicOr(&c.counters[kOpenOvf], (int)nc);
+        }
+#endif
+        const uint32_t sk = sub_sort_pk2(e.mask, lane, bin0, bin1, has2, my_cls, my_w);
+        sub_post_pk(c, s, cnt, lane, sk & 0xFFFFu, g, bb, nc, tcw);
+        if (nc) {
+          ++nonconst;
+          if (bb >= 0 && g > best_g) { best_g = g; best_f = f0; best_b = bb; }
+        }
+        if (has2 && nonconst < s.max_features) {
+          sub_post_pk(c, s, cnt, lane, sk >> 16, g, bb, nc, tcw);
+          if (nc) {
+            ++nonconst;
+            if (bb >= 0 && g > best_g) { best_g = g; best_f = f1; best_b = bb; }
+          }
+        }
+      }
     } else
     for (int pos = 0; nonconst < s.max_features && pos < d; ++pos) {
       const int f = feature_at(fp, pos, d);
@@ -4199,6 +4433,19 @@ __global__ void k_test_wave_prims(const uint32_t* in, uint32_t* out) {
   o[10 * 64 + lane] = (uint32_t)wave::min_u64(((uint64_t)v << 32) | (uint32_t)lane, lane);
 }
 
+// the packed 16-bit sorts (tests/test_forest_subtree_pk16_gpu.py): each lane's word holds two
+// independent keys.  out layout per block of 64: [64-lane sort | WD = 8 | WD = 16 | WD = 32
+// segment sorts], every key half ascending over the wave / over each segment
+__global__ void k_test_pk16_sorts(const uint32_t* in, uint32_t* out) {
+  const int lane = threadIdx.x;
+  const uint32_t v = in[blockIdx.x * 64 + lane];
+  uint32_t* o = out + (size_t)blockIdx.x * 64 * 4;
+  o[0 * 64 + lane] = wave::bitonic64_pk16(v, lane);
+  o[1 * 64 + lane] = bitonic_seg_pk16<8>(v, lane);
+  o[2 * 64 + lane] = bitonic_seg_pk16<16>(v, lane);
+  o[3 * 64 + lane] = bitonic_seg_pk16<32>(v, lane);
+}
+
 struct PredictArgs;
 extern "C" int dml_forest_predict_fit(const PredictArgs* a, int32_t f, hipStream_t st);
 
@@ -4221,6 +4468,11 @@ int dml_test_wave_prims(const uint32_t* in, uint32_t* out, int64_t nblocks, hipS
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
+int dml_test_pk16_sorts(const uint32_t* in, uint32_t* out, int64_t nblocks, hipStream_t st) {
+  k_test_pk16_sorts<<<(unsigned)nblocks, 64, 0, st>>>(in, out);
+  return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
 const char* dml_forest_last_error(int* line) {
   if (line) *line = g_last_err_line;
   return hipGetErrorString(g_last_err);
@@ -4232,6 +4484,8 @@ int dml_forest_wave_hist32() { return DML_WAVE_HIST32 != 0 ? 1 : 0; }
 int dml_forest_large_stash() { return DML_LARGE_STASH != 0 ? 1 : 0; }
 // 1: the block tier stashes its first group's bins as dword planes (DML_BLOCK_STASH_PLANES)
 int dml_forest_block_stash_planes() { return DML_BLOCK_STASH_PLANES != 0 ? 1 : 0; }
+// 1: binary subtrees sort two features per pass with packed 16-bit keys (DML_SUB_PK16)
+int dml_forest_sub_pk16() { return DML_SUB_PK16 != 0 ? 1 : 0; }
 int dml_forest_sizeof_treespec() { return (int)sizeof(TreeSpec); }
 int dml_forest_sizeof_args() { return (int)sizeof(ForestArgs); }
 int dml_forest_sizeof_node() { return (int)sizeof(NodeRec); }

@@ -192,6 +192,28 @@ DML_HD uint32_t bin32_w0(uint32_t v) { return v & kPack32Mask12; }
 DML_HD uint32_t bin32_w1(uint32_t v) { return (v >> 12) & kPack32Mask12; }
 DML_HD uint32_t bin32_rows(uint32_t v) { return v >> 24; }
 
+// ---- subtree tier, binary classification: a row's sort key in 16 bits -----------------
+// bin in bits 5-12, class in bit 4, bootstrap weight in bits 0-3: two features' keys share a
+// register and one packed sorting network (wave_ops.h bitonic64_pk16) sorts both.  An absent
+// row (lane outside the node) is kPk16Absent, above every real key.  After the sort the
+// class and the weight are read back from the key, so rows of equal keys are interchangeable.
+// The sorted rows' weights are scanned as pk16_scan_word: all weight in bits 0-15, class 1's
+// in bits 16-31; a subtree node has at most kPk16MaxRows rows.
+constexpr int kPk16ClsShift = kRowWeightBits, kPk16BinShift = kRowWeightBits + 1;
+constexpr int kPk16MaxRows = 64;
+constexpr uint32_t kPk16Absent = 0xFFFFu;
+static_assert(kPoisTable < (1 << kPk16ClsShift), "a bootstrap weight must fit the 16-bit key's weight field");
+static_assert(((255u << kPk16BinShift) | (1u << kPk16ClsShift) | (uint32_t)(kPack32MaxWeight - 1)) < kPk16Absent,
+              "every real 16-bit key must sort below an absent row's");
+static_assert(kPk16MaxRows * (kPack32MaxWeight - 1) < 65536, "a 64-row node's weight must fit the packed scan's 16-bit fields");
+DML_HD uint32_t pk16_key(int bin, int cls, uint32_t w) {
+  return ((uint32_t)bin << kPk16BinShift) | ((uint32_t)cls << kPk16ClsShift) | (w & (uint32_t)(kPack32MaxWeight - 1));
+}
+DML_HD int pk16_bin(uint32_t k) { return (int)(k >> kPk16BinShift); }
+DML_HD int pk16_cls(uint32_t k) { return (int)((k >> kPk16ClsShift) & 1u); }
+DML_HD uint32_t pk16_w(uint32_t k) { return k & (uint32_t)(kPack32MaxWeight - 1); }
+DML_HD uint32_t pk16_scan_word(int cls, uint32_t w) { return w | (cls == 1 ? w << 16 : 0u); }
+
 // fields of a packed binary histogram word of either width (CT: the u64 word or the u32 one)
 template <class CT>
 DML_HD uint32_t pk_w0(CT v) {

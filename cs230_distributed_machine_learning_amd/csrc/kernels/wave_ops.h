@@ -166,6 +166,50 @@ __device__ __forceinline__ uint32_t bitonic64(uint32_t key, int lane) {
   return key;
 }
 
+// two 16-bit keys per lane, bits 0-15 and 16-31: the halves are compared independently
+// (v_pk_min_u16 / v_pk_max_u16) and travel together
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b) {
+  return __builtin_bit_cast(uint32_t, __builtin_elementwise_min(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+}
+__device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b) {
+  return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+}
+
+// one compare-exchange of the packed networks with partner lane ^ J inside ascending /
+// descending blocks of K lanes (K >= WD: every block ascends)
+template <int WD, int K, int J>
+__device__ __forceinline__ uint32_t pk16_step(uint32_t key, int lane) {
+  const uint32_t other = xor32<J>(key, lane);
+  const bool up = K >= WD ? true : ((lane & K) == 0);
+  const bool lower = (lane & J) == 0;
+  const uint32_t mn = pk_min_u16(key, other), mx = pk_max_u16(key, other);
+  return (lower == up) ? mn : mx;
+}
+
+// bitonic64's network on two independent 16-bit keys per lane, over segments of WD = 8, 16, 32
+// or 64 lanes: each half comes out ascending over the lanes of its segment.  Which of (min,
+// max) a lane keeps depends on the lane alone, so the halves share the select: one exchange,
+// one packed min, one packed max and one select per step sort both.  Equal keys may tie (the
+// callers' rows of equal keys are interchangeable).
+template <int WD>
+__device__ __forceinline__ uint32_t bitonic_pk16(uint32_t key, int lane) {
+  static_assert(WD == 8 || WD == 16 || WD == 32 || WD == 64, "segments of 8, 16, 32 or 64 lanes");
+#define DML_PK_STEP(K, J) key = pk16_step<WD, K, J>(key, lane);
+  DML_PK_STEP(2, 1)
+  DML_PK_STEP(4, 2) DML_PK_STEP(4, 1)
+  DML_PK_STEP(8, 4) DML_PK_STEP(8, 2) DML_PK_STEP(8, 1)
+  if constexpr (WD >= 16) { DML_PK_STEP(16, 8) DML_PK_STEP(16, 4) DML_PK_STEP(16, 2) DML_PK_STEP(16, 1) }
+  if constexpr (WD >= 32) { DML_PK_STEP(32, 16) DML_PK_STEP(32, 8) DML_PK_STEP(32, 4) DML_PK_STEP(32, 2) DML_PK_STEP(32, 1) }
+  if constexpr (WD >= 64) {
+    DML_PK_STEP(64, 32) DML_PK_STEP(64, 16) DML_PK_STEP(64, 8) DML_PK_STEP(64, 4) DML_PK_STEP(64, 2) DML_PK_STEP(64, 1)
+  }
+#undef DML_PK_STEP
+  return key;
+}
+
+__device__ __forceinline__ uint32_t bitonic64_pk16(uint32_t key, int lane) { return bitonic_pk16<64>(key, lane); }
+
 // argmax over (gain desc, idx asc) — every lane ends with the same pair
 __device__ __forceinline__ void argmax(double& g, int& idx, int lane) {
 #define DML_ARGMAX_STEP(M)                                           \

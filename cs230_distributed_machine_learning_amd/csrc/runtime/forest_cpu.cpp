@@ -458,6 +458,21 @@ void dml_bin32_fields(uint32_t v, uint32_t* out) {
 }
 void dml_pack32_limits(int32_t* out) { out[0] = kPack32MaxRows; out[1] = kPack32MaxWeight; out[2] = kPoisTable; }
 
+// the subtree tier's 16-bit sort key and packed scan word (forest_common.h pk16_*), for host
+// tests of the text the HIP kernels compile
+uint32_t dml_pk16_key(int32_t bin, int32_t cls, uint32_t w) { return pk16_key(bin, cls, w); }
+void dml_pk16_fields(uint32_t k, uint32_t* out) { out[0] = (uint32_t)pk16_bin(k); out[1] = (uint32_t)pk16_cls(k); out[2] = pk16_w(k); }
+uint32_t dml_pk16_scan_word(int32_t cls, uint32_t w) { return pk16_scan_word(cls, w); }
+void dml_pk16_limits(int32_t* out) { out[0] = kPk16MaxRows; out[1] = (int32_t)kPk16Absent; out[2] = kPoisTable; }
+// a node's key (the root's from the tree seed, a child's from its parent's) and its feature
+// visiting order, for tests that need to know which feature a builder meets at which position
+uint64_t dml_node_root_key(uint64_t seed) { return root_key(seed); }
+uint64_t dml_node_child_key(uint64_t parent, int32_t side) { return child_key(parent, side); }
+void dml_node_visit_order(uint64_t key, int32_t d, int32_t* out) {
+  const FeatPerm fp = feat_perm(key, d);
+  for (int32_t k = 0; k < d; ++k) out[k] = feature_at(fp, k, d);
+}
+
 // the block tier's dword-plane bin stash (forest_common.h stash_plane_*), for host tests of the
 // address arithmetic the HIP kernels compile: the number of planes of a g-position group, a
 // plane's first byte, and the byte of every (row position p, visiting position q) of a node,

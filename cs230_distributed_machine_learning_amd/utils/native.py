@@ -248,6 +248,7 @@ def _register_optional(lib) -> None:
         "dml_exp_hist": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
         "dml_forest_release_scratch": (c_i32, []),
         "dml_forest_block_stash_planes": (c_i32, []),
+        "dml_forest_sub_pk16": (c_i32, []),
         "dml_mae_sizeof_args": (c_i32, []),
         "dml_mae_sizeof_open": (c_i32, []),
         "dml_mae_sizeof_res": (c_i32, []),
