@@ -33,12 +33,6 @@
 #include "forest_common.h"
 #include "wave_ops.h"
 
-#ifndef DML_RPT_BLOCK
-#define DML_RPT_BLOCK 1
-#endif
-#if DML_RPT_BLOCK < 1 || DML_RPT_BLOCK > 4
-#error "DML_RPT_BLOCK must be 1..4"
-#endif
 #ifndef DML_BLOCK_NT
 // threads per block-tier node of a binary-classification build: 2 waves.  With the LDS slab
 // sized to the batch's max_features (10: 22 KB) 7 nodes share a CU instead of 4 at 256
@@ -50,9 +44,9 @@
 #endif
 template <int MODE> constexpr int block_nt() { return MODE == 1 ? DML_BLOCK_NT : 256; }
 #ifndef DML_NODES_WPE
-// block tier (binary): 4 waves per SIMD = 4 workgroups per CU.  With the register-rows paths
-// compiled out (DML_BLOCK_STREAM_ONLY) and the window loop's bins packed 4 per register the
-// kernel fits 127 VGPRs without spills (it needed 168 at 3 waves before): sweep build
+// block tier (binary): 4 waves per SIMD = 4 workgroups per CU.  The tier streams its rows (no
+// register-rows path) and with the window loop's bins packed 4 per register the kernel fits
+// 127 VGPRs without spills (it needed 168 at 3 waves before): sweep build
 // 1.029 -> 1.008 s (profiles/r5_block_occupancy.txt)
 #define DML_NODES_WPE 4
 #endif
@@ -88,12 +82,6 @@ template <int MODE> constexpr int block_nt() { return MODE == 1 ? DML_BLOCK_NT :
 // 0: the 16-B slots (A/B builds; docs/BLOCK_STASH.md)
 #define DML_BLOCK_STASH_PLANES 1
 #endif
-#ifndef DML_BLOCK_PART_ALL
-// block tier: 1 takes the two-pass partition for every node whose flags fit the dead histogram
-// LDS (the group-offset scan walks ceil(ngrp / NT) groups per thread), 0 only for nodes of
-// <= 128 NT rows, two groups per thread (docs/BLOCK_STASH.md, part 2)
-#define DML_BLOCK_PART_ALL 1
-#endif
 #ifndef DML_PART_KEEP
 #define DML_PART_KEEP 2        // block-tier partition: rounds whose row ids pass 1 keeps in registers (0/1/2: 1.018/1.014/1.009 s sweep build, r5 e6)
 #endif
@@ -105,9 +93,6 @@ template <int MODE> constexpr int block_nt() { return MODE == 1 ? DML_BLOCK_NT :
 #endif
 #ifndef DML_KGMAX_BLOCK
 #define DML_KGMAX_BLOCK 16     // block tier: largest feature group with register-resident bins
-#endif
-#ifndef DML_BLOCK_STREAM_ONLY
-#define DML_BLOCK_STREAM_ONLY 1   // block-tier nodes (> wave_max >= 256 rows) always stream their rows
 #endif
 #ifndef DML_NODES_WPE_REG
 #define DML_NODES_WPE_REG 2   // regression node kernels: 3 histogram planes + payloads fit 256 VGPRs, no spills
@@ -152,24 +137,8 @@ template <int MODE> constexpr int block_nt() { return MODE == 1 ? DML_BLOCK_NT :
 #ifndef DML_GINI_PF
 #define DML_GINI_PF 1          // binary Gini: fp32 pre-filter of candidate bins (eval_feature)
 #endif
-#ifndef DML_EVAL_PAIRS
-#define DML_EVAL_PAIRS 0       // k_nodes: binary-Gini features evaluated two at a time (1 both tiers, 2 wave, 3 block; slower)
-#endif
 #ifndef DML_WAVE_PREFETCH
 #define DML_WAVE_PREFETCH 12   // wave tier: visiting positions whose bins are gathered up front
-#endif
-// large-tier grids: node index fastest (1) so chunk c of EVERY large node is in flight at
-// once -- at the top levels the rows behind chunk c of all trees of a fold are nearly the
-// same rows, so those table lines are served from the XCD's L2 -- or chunk fastest (0)
-#ifndef DML_LARGE_NODE_FAST
-#define DML_LARGE_NODE_FAST 1
-#endif
-#if DML_LARGE_NODE_FAST
-#define DML_LSLOT ((int)blockIdx.x)
-#define DML_LCHUNK ((int)blockIdx.y)
-#else
-#define DML_LSLOT ((int)blockIdx.y)
-#define DML_LCHUNK ((int)blockIdx.x)
 #endif
 
 // optional per-phase cycle accounting of the fused node kernel (-DDML_PHASE_PROF builds only)
@@ -624,6 +593,9 @@ __device__ __forceinline__ bool gini_pf_ok(const NodeSpec& s, double cw0, double
 // bin's, which wins the tie (lowest bin), so the split chosen is unchanged; what is left is
 // usually one contender per lane, re-scored in one pass.
 // CT: the packed word, u64 (21/21/22-bit fields) or the wave tier's u32 (12/12/8, pack_bin32).
+// Only NF = 1 is instantiated (the pairwise caller is gone).  The [NF] arrays stay for now: written
+// as scalars, statement for statement, the six binary k_nodes kernels and k_bigsub compile to
+// 9 .. 14 instructions less each -- a change to this tier's critical path to make with a benchmark.
 template <int NF, int FS, class CT = unsigned long long>
 __device__ DML_EVAL_ATTR void eval_gini_pf(CT* h, int span, const NodeSpec& s, int lane,
                                            double* out_gain, int* out_bin, int* out_nc, double* out_left, int CH,
@@ -1280,8 +1252,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
   using CT = typename std::conditional<H32, uint32_t, typename HT<MODE>::T>::type;
   constexpr bool PK = FC >= 0;   // specialised builds have packed row words
   constexpr int NW = NT / 64;
-  constexpr int RPT = NT == 64 ? 4 : DML_RPT_BLOCK;   // rows per thread in registers (<= 4: packed u8 x 4)
-  static_assert(RPT >= 1 && RPT <= 4, "RPT");
+  constexpr int RPT = NT == 64 ? 4 : 1;   // wave tier: rows per thread in registers (packed u8 x 4)
   static_assert(2 * RPT * (NT / 64) <= 32, "Scratch::wcnt too small for this NT x RPT");
   constexpr int KGMAX = NT == 64 ? (H32 ? DML_KGMAX_WAVE32 : DML_KGMAX_WAVE) : DML_KGMAX_BLOCK;   // feature-group bound (register-resident bins)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1326,12 +1297,12 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
   constexpr bool PLANES = NT > 64 && DML_BLOCK_STASH_PLANES != 0;
   uint8_t* const stash0 = c.bscr + stash_plane_base(on.start, cnt, 0);
   auto plane = [&](int w) -> uint8_t* { return stash0 + 4 * (int64_t)cnt * w; };
-  // rows (+ bootstrap weight + label payload) of a <= NT*RPT-row node stay in registers
-  // for every feature group and the partition; larger nodes stream in NT*RPT chunks.
-  // (block tier, DML_BLOCK_STREAM_ONLY: nodes there have > wave_max >= NT rows, so the
-  // register-rows paths are compiled out of it -- their registers no longer bound its occupancy)
-  // (narrow word: the launcher sends it only builds with wave_max <= kPack32MaxRows < NT * RPT)
-  const bool reg_rows = (NT > 64 && DML_BLOCK_STREAM_ONLY) ? false : (H32 || cnt <= NT * RPT);
+  // wave tier: rows (+ bootstrap weight + label payload) of a <= NT*RPT-row node stay in
+  // registers for every feature group and the partition; larger nodes stream in NT*RPT chunks
+  // (narrow word: the launcher sends it only builds with wave_max <= kPack32MaxRows < NT * RPT).
+  // The block tier always streams: its nodes have > wave_max >= NT rows, and without a
+  // register-rows path those registers do not bound its occupancy
+  const bool reg_rows = NT == 64 && (H32 || cnt <= NT * RPT);
   uint32_t rrow[RPT], rbin[RPT];
   using PL = typename std::conditional<H32, uint32_t, typename PLT<MODE>::T>::type;
   PL rpl[RPT];
@@ -1365,7 +1336,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
   // wave tier, register rows: the bins of the first KPRE visiting positions are gathered
   // ONCE, all in flight together, before the first feature group -- the later groups
   // (KG histograms at a time fit LDS) then start without another gather round trip
-  constexpr int KPRE = (NT == 64 && RPT == 4) ? DML_WAVE_PREFETCH : 0;
+  constexpr int KPRE = NT == 64 ? DML_WAVE_PREFETCH : 0;
   uint32_t pre[KPRE > 0 ? KPRE : 1];
   int npre = 0;
   if constexpr (KPRE > 0) {
@@ -1454,8 +1425,8 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
         }
       }
     } else
-    if (!reg_rows && RPT == 1) {
-      // large node, one row per thread per NT-row chunk, software-pipelined over chunks with
+    if (NT > 64) {
+      // block tier, one row per thread per NT-row chunk, software-pipelined over chunks with
       // two register sets (A: even chunks, B: odd chunks) that swap roles without copies: per
       // chunk, the row id two chunks ahead is loaded first, then the next chunk's bins are
       // gathered, then this chunk's histogram atomics run -- so waiting for this chunk's bins
@@ -1644,25 +1615,6 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
             if (rrow[u] != 0xFFFFFFFFu) hist_add<MODE>(hj, c, (int)bins[j][u], rpl[u]);
         }
       }
-      if (NT > 64 && !reg_rows && pos == 0) {
-        // streamed block-tier node, RPT rows per thread: the first group's bins (<= 16
-        // visiting positions) into each row's scratch slot, as the one-row pipeline does
-#pragma unroll
-        for (int u = 0; u < RPT; ++u)
-          if (rrow[u] != 0xFFFFFFFFu) {
-            uint32_t w4[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int j = 0; j < KGMAX && j < 16; ++j)
-              if (j < g) w4[j >> 2] |= (bins[j][u] & 0xFFu) << (8 * (j & 3));
-            if constexpr (PLANES) {
-#pragma unroll
-              for (int w = 0; w < stash_planes(KGMAX); ++w)
-                if (4 * w < g) *plane_word(plane(w), base + tid + NT * u) = w4[w];
-            } else {
-              *(uint4*)(c.bscr + (on.start + base + tid + NT * u) * 16) = make_uint4(w4[0], w4[1], w4[2], w4[3]);
-            }
-          }
-      }
       if (NT == 64 && !reg_rows && pos < 16) {
         // streamed wave-tier node: this group's bins at byte (visiting position) of the slot
 #pragma unroll
@@ -1687,21 +1639,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
     }
     __syncthreads();
     PH(2)
-    int j0 = wid;
-#if !defined(DML_X2_EVAL) && DML_EVAL_PAIRS
-    if constexpr (MODE == 1 && (DML_EVAL_PAIRS == 1 || (DML_EVAL_PAIRS == 2) == (NT == 64))) {
-      // features j and j + NW evaluated together (two interleaved chains)
-      const double* cw = tree_cw<FC>(c, on.tree);
-      if (gini_pf_ok(s, cwk(cw, 0), cwk(cw, 1)))
-        for (; j0 + NW < g; j0 += 2 * NW) {
-          if (mono_of<FC>(c, s, feats[j0]) != 0 || mono_of<FC>(c, s, feats[j0 + NW]) != 0) break;
-          eval_gini_pf<2, NW, CT>(hist + j0 * span, span, s, lane, rg + j0, rb + j0, rn + j0, rleft + j0 * c.CH, c.CH, true,
-                              cwk(cw, 0), cwk(cw, 1));
-          if (lane == 0) { rmid[j0] = 0.0; rmid[j0 + NW] = 0.0; }
-        }
-    }
-#endif
-    for (int j = j0; j < g; j += NW) {
+    for (int j = wid; j < g; j += NW) {
 #ifdef DML_X2_EVAL   // sensitivity build: every feature evaluated twice (the first keeps the histogram)
       eval_feature<MODE, 3, CT>(hist + j * span, c.C, c.CH, s, lane, rg + j, rb + j, rn + j, rleft + j * c.CH, false,
                          tree_cw<FC>(c, on.tree), &c.rq, MonoQ{mono_of<FC>(c, s, feats[j]), sc->lo, sc->hi}, rmid + j);
@@ -1802,11 +1740,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
 #ifdef DML_X2_PART   // sensitivity build: the (idempotent) partition pass runs twice
   for (int rep_ = 0; rep_ < 2; ++rep_) {
 #endif
-  if (NT > 64 && !reg_rows && (DML_BLOCK_PART_ALL || cnt <= 128 * NT) &&
-      (size_t)((cnt + 63) / 64) * 12 <= (size_t)KG * span * sizeof(CT)) {
-    // block tier, streamed node: two passes and two barriers for the whole node (not two per
-    // chunk).  Pass 1 ranks every row (split bin from the histogram pass's scratch, else
-    // gathered) into one ballot word per 64-row group in LDS (the histograms are dead);
+  if (NT > 64 && (size_t)((cnt + 63) / 64) * 12 <= (size_t)KG * span * sizeof(CT)) {
+    // block tier, node whose flags fit the dead histogram LDS: two passes and two barriers for
+    // the whole node (not two per chunk).  Pass 1 ranks every row (split bin from the histogram
+    // pass's scratch, else gathered) into one ballot word per 64-row group in LDS;
     // one block scan gives every group's left offset; pass 2 re-reads the row ids
     // (coalesced) and writes each row at its stable rank.
     uint64_t* lflag = (uint64_t*)hist;                        // [ngrp] left flags
@@ -1855,30 +1792,17 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
     // exclusive prefix of the groups' left counts: thread t owns groups [gpt t, gpt (t + 1)),
     // gpt = ceil(ngrp / NT) of them (8 at 65 536 rows and 128 threads), so no group of a node
     // whose flags fit the LDS is left unranked whatever block_max is
-    if constexpr (DML_BLOCK_PART_ALL) {
-      const int gpt = (ngrp + NT - 1) / NT, gb = gpt * tid;
-      int tot = 0;
-      for (int i = 0; i < gpt; ++i) tot += gb + i < ngrp ? __popcll(lflag[gb + i]) : 0;
-      const int incl = wave::incl_scan<int>(tot);
-      if (lane == 63) sc->wcnt[wid] = incl;
-      __syncthreads();
-      int ex = incl - tot;
-      for (int w = 0; w < wid; ++w) ex += sc->wcnt[w];
-      for (int i = 0; i < gpt && gb + i < ngrp; ++i) {
-        loff[gb + i] = ex;
-        ex += __popcll(lflag[gb + i]);
-      }
-    } else {   // <= 2 NT groups: two per thread
-      const int g0 = 2 * tid, g1 = 2 * tid + 1;
-      const int c0 = g0 < ngrp ? __popcll(lflag[g0]) : 0, c1 = g1 < ngrp ? __popcll(lflag[g1]) : 0;
-      const int incl = wave::incl_scan<int>(c0 + c1);
-      if (lane == 63) sc->wcnt[wid] = incl;
-      __syncthreads();
-      int wbase = 0;
-      for (int w = 0; w < wid; ++w) wbase += sc->wcnt[w];
-      const int ex = wbase + incl - (c0 + c1);
-      if (g0 < ngrp) loff[g0] = ex;
-      if (g1 < ngrp) loff[g1] = ex + c0;
+    const int gpt = (ngrp + NT - 1) / NT, gb = gpt * tid;
+    int tot = 0;
+    for (int i = 0; i < gpt; ++i) tot += gb + i < ngrp ? __popcll(lflag[gb + i]) : 0;
+    const int incl = wave::incl_scan<int>(tot);
+    if (lane == 63) sc->wcnt[wid] = incl;
+    __syncthreads();
+    int ex = incl - tot;
+    for (int w = 0; w < wid; ++w) ex += sc->wcnt[w];
+    for (int i = 0; i < gpt && gb + i < ngrp; ++i) {
+      loff[gb + i] = ex;
+      ex += __popcll(lflag[gb + i]);
     }
     __syncthreads();
     // pass 2, U2 positions per thread per round: the row-id loads of a round are issued
@@ -1928,24 +1852,22 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
     return (uint32_t)c.Xb[(int64_t)(r & c.rmask) * c.ld + feat];
   };
   uint32_t nrow = INVR, nbin = 0, frow = INVR;
-  if (!reg_rows && RPT == 1) {
+  if (NT > 64) {
     rrow[0] = prow(tid);
     rbin[0] = pbin(tid, rrow[0]);
     nrow = prow(NT + tid);
   }
   for (int cb = 0; cb < cnt; cb += NT * RPT) {
-    if (!reg_rows) {
-      if constexpr (RPT == 1) {
-        nbin = pbin(cb + NT + tid, nrow);
-        frow = prow(cb + 2 * NT + tid);
-      } else {
-        load_rows(cb);
+    if constexpr (NT > 64) {
+      nbin = pbin(cb + NT + tid, nrow);
+      frow = prow(cb + 2 * NT + tid);
+    } else if (!reg_rows) {
+      load_rows(cb);
 #pragma unroll
-        for (int u = 0; u < RPT; ++u)
-          rbin[u] = rrow[u] == 0xFFFFFFFFu ? 0u
-                  : bj_scr >= 0 ? pbin(cb + tid + NT * u, rrow[u])
-                                : (uint32_t)c.Xb[(int64_t)(rrow[u] & c.rmask) * c.ld + feat];
-      }
+      for (int u = 0; u < RPT; ++u)
+        rbin[u] = rrow[u] == 0xFFFFFFFFu ? 0u
+                : bj_scr >= 0 ? pbin(cb + tid + NT * u, rrow[u])
+                              : (uint32_t)c.Xb[(int64_t)(rrow[u] & c.rmask) * c.ld + feat];
     }
     uint64_t ml[RPT], mr[RPT];
 #pragma unroll
@@ -1991,9 +1913,9 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
       else out[nl + baseR + offR[u] + lane_prefix(mr[u])] = rrow[u];
     }
     baseL += totL; baseR += totR;
-    if (!reg_rows && RPT == 1) { rrow[0] = nrow; rbin[0] = nbin; nrow = frow; }
+    if (NT > 64) { rrow[0] = nrow; rbin[0] = nbin; nrow = frow; }
   }
-  }   // streamed block-tier / register-rows partition
+  }   // two-pass block-tier / chunked partition
 #ifdef DML_X2_PART
   }
 #endif
@@ -3237,7 +3159,7 @@ template <int MODE, bool PK>
 __global__ __launch_bounds__(256) void k_hist_large(Ctx c, int fround) {
   using CT = typename HT<MODE>::T;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  const int slot = DML_LSLOT;
+  const int slot = (int)blockIdx.x, lchunk = (int)blockIdx.y;   // grid: (node, row chunk)
   const LState& st = c.lstate[slot];
   // node state read once (the loop's bscr stores could alias it: a reference would reload it)
   const int st_pos = fround >= 0 ? fround : __builtin_amdgcn_readfirstlane(st.pos);
@@ -3246,7 +3168,7 @@ __global__ __launch_bounds__(256) void k_hist_large(Ctx c, int fround) {
   // (LState::scr_id), at a feature-subset round only when the partition reads them (large_stash)
   const bool stash = __builtin_amdgcn_readfirstlane((st_pos == 0 && (fround >= 0 || large_stash(c))) ? 1 : 0) != 0;
   if (st.done || (fround >= 0 && st.derive)) return;
-  const int r0 = DML_LCHUNK * c.chunk;
+  const int r0 = lchunk * c.chunk;
   if (r0 >= st.on.count) return;
   const int r1 = min(r0 + c.chunk, st.on.count);
   const NodeSpec s = spec_of<-1>(c, st.on.tree);
@@ -3731,10 +3653,10 @@ __global__ __launch_bounds__(256) void k_partition_large(Ctx c) {
   // pass 1 ranks the chunk's rows (split bins prefetched one step ahead, flags kept in LDS)
   // and reserves the chunk's left/right ranges with ONE atomic pair; pass 2 writes the rows
   // at ballot/prefix offsets (no global atomics per 256 rows)
-  const int slot = DML_LSLOT;
+  const int slot = (int)blockIdx.x, lchunk = (int)blockIdx.y;   // grid: (node, row chunk)
   const LState& st = c.lstate[slot];
   if (!st.split) return;
-  const int r0 = DML_LCHUNK * c.chunk;
+  const int r0 = lchunk * c.chunk;
   if (r0 >= st.on.count) return;
   const int r1 = min(r0 + c.chunk, st.on.count);
   const int feat = st.best_feat, bin = st.best_bin, nl = st.nl;
@@ -4603,6 +4525,9 @@ static int build_impl(ForestArgs* a, hipStream_t st) {
     }
   }
   const unsigned nchunks = (unsigned)((a->max_active + a->chunk - 1) / a->chunk);
+  // whole-histogram levels (below): read once per build (tests change DML_LARGE_SUB between builds)
+  const bool sub_on = !getenv("DML_LARGE_SUB") || atoi(getenv("DML_LARGE_SUB")) != 0;
+  const double sub_gb = getenv("DML_LARGE_SUB_GB") ? atof(getenv("DML_LARGE_SUB_GB")) : 4.0;
   int cur = 0, levels = 0, large_rounds = 0;
   int fpar = 0;             // whole-histogram buffer parity of this level
   bool prev_full = false;   // the previous level kept its large nodes' whole histograms
@@ -4685,8 +4610,6 @@ static int build_impl(ForestArgs* a, hipStream_t st) {
     // histograms over all d features fit the budget -> keep them, and derive the larger of
     // two large siblings at the next level from its parent's (DML_LARGE_SUB=0: off)
     const size_t full_node_b = (size_t)a->d * ghist_feat_bytes(MODE, CH);
-    const bool sub_on = !getenv("DML_LARGE_SUB") || atoi(getenv("DML_LARGE_SUB")) != 0;
-    const double sub_gb = getenv("DML_LARGE_SUB_GB") ? atof(getenv("DML_LARGE_SUB_GB")) : 4.0;
     bool full = sub_on && nL > 0 && a->all_features && (double)nL * full_node_b <= sub_gb * 1e9;
     FullBufs* fb = full ? full_bufs() : nullptr;
     if (full && (!fb || !ensure_bytes(fb->gf[fpar], fb->gf_bytes[fpar], (size_t)nL * full_node_b))) full = false;
@@ -4719,12 +4642,15 @@ static int build_impl(ForestArgs* a, hipStream_t st) {
                             ns + ns4 + nw + nb == 0;
     c.root_counts = root_cache ? (uint32_t*)a->root_counts : nullptr;
     c.root_cnt_skip = root_cache && a->root_counts_valid ? 1 : 0;
+    // the two row passes' grid, (node, row chunk): node index fastest, so chunk c of EVERY large
+    // node is in flight at once -- at the top levels the rows behind chunk c of all trees of a
+    // fold are nearly the same rows, so those table lines are served from the XCD's L2
+    const dim3 glarge((unsigned)nL, nchunks);
     if (nL && full) {
       k_large_prep<<<nL, 64, 0, st>>>(c, cur, nL);
       const int rounds = (int)((a->d + a->kg_large - 1) / a->kg_large);
       HIP_OK(hipMemsetAsync(c.gf_cur, 0, (size_t)nL * full_node_b, st));
       if (c.root_cnt_skip) k_root_counts<<<dim3((unsigned)nL, (unsigned)a->d), 256, 0, st>>>(c, 0);
-      const dim3 gh = DML_LARGE_NODE_FAST ? dim3((unsigned)nL, nchunks) : dim3(nchunks, (unsigned)nL);
       // below the top two levels a node may be a row-window node with kg_rw-wide rounds: the
       // rounds' LDS covers kg_rw features (its later rounds exit at once for such nodes)
       Ctx cr = c;
@@ -4732,8 +4658,8 @@ static int build_impl(ForestArgs* a, hipStream_t st) {
       const size_t lds_round = cr.kg_rw > 0 ? lds_hl_rw : lds_hl;
       for (int round = 0; round < rounds; ++round) {
         ++large_rounds;
-        if (c.packed) k_hist_large<MODE, true><<<gh, 256, lds_round, st>>>(cr, round);
-        else k_hist_large<MODE, false><<<gh, 256, lds_round, st>>>(cr, round);
+        if (c.packed) k_hist_large<MODE, true><<<glarge, 256, lds_round, st>>>(cr, round);
+        else k_hist_large<MODE, false><<<glarge, 256, lds_round, st>>>(cr, round);
       }
       if (root_cache && !c.root_cnt_skip) {
         k_root_counts<<<dim3((unsigned)nL, (unsigned)a->d), 256, 0, st>>>(c, 1);
@@ -4753,8 +4679,7 @@ static int build_impl(ForestArgs* a, hipStream_t st) {
       } else {
         for (int round = 0; round < rounds; ++round) k_split_large<GM><<<nL, 256, lds_sl, st>>>(c, cur);
       }
-      const dim3 gp = DML_LARGE_NODE_FAST ? dim3((unsigned)nL, nchunks) : dim3(nchunks, (unsigned)nL);
-      k_partition_large<<<gp, 256, (size_t)((a->chunk + 255) / 256) * 4 * 8, st>>>(c);
+      k_partition_large<<<glarge, 256, (size_t)((a->chunk + 255) / 256) * 4 * 8, st>>>(c);
       if (reg) k_large_finish<<<nL, 64, 0, st>>>(c, cur);
     } else if (nL) {
       k_large_prep<<<nL, 64, 0, st>>>(c, cur, nL);
@@ -4763,9 +4688,8 @@ static int build_impl(ForestArgs* a, hipStream_t st) {
         ++large_rounds;
         HIP_OK(hipMemsetAsync(c.ghist, 0, (size_t)nL * a->kg_large * ghist_feat_bytes(MODE, CH), st));
         HIP_OK(hipMemsetAsync(c.counters + kNeedMore, 0, 4, st));
-        const dim3 gh = DML_LARGE_NODE_FAST ? dim3((unsigned)nL, nchunks) : dim3(nchunks, (unsigned)nL);
-        if (c.packed) k_hist_large<MODE, true><<<gh, 256, lds_hl, st>>>(c, -1);
-        else k_hist_large<MODE, false><<<gh, 256, lds_hl, st>>>(c, -1);
+        if (c.packed) k_hist_large<MODE, true><<<glarge, 256, lds_hl, st>>>(c, -1);
+        else k_hist_large<MODE, false><<<glarge, 256, lds_hl, st>>>(c, -1);
         k_split_large<GM><<<nL, 256, lds_sl, st>>>(c, cur);
         if (fixed_rounds) {   // every node visits every feature: the round count is known
           if (round + 1 >= fixed_rounds) break;
@@ -4775,8 +4699,7 @@ static int build_impl(ForestArgs* a, hipStream_t st) {
         HIP_OK(hipStreamSynchronize(st));
         if (!h[32]) break;
       }
-      const dim3 gp = DML_LARGE_NODE_FAST ? dim3((unsigned)nL, nchunks) : dim3(nchunks, (unsigned)nL);
-      k_partition_large<<<gp, 256, (size_t)((a->chunk + 255) / 256) * 4 * 8, st>>>(c);
+      k_partition_large<<<glarge, 256, (size_t)((a->chunk + 255) / 256) * 4 * 8, st>>>(c);
       if (reg) k_large_finish<<<nL, 64, 0, st>>>(c, cur);
     }
     if (fork) {
