@@ -118,6 +118,16 @@ DML_HD uint32_t boot_weight(const TS& t, uint32_t row) {
   return k;
 }
 
+// boot_weight(t, row) == 0 ("row is out of bag for the tree") from the row's boot_row_key:
+// one splitmix64 per (row, tree) and one compare -- the Poisson weight is 0 iff u is below the
+// table's first entry, the Bernoulli subsample's (bootstrap == 2) iff u is NOT below it
+template <class TS>
+DML_HD bool boot_is_oob(const TS& t, uint64_t row_key) {
+  if (!t.bootstrap) return false;
+  const uint32_t u = (uint32_t)(splitmix64(t.seed ^ row_key) >> 32);
+  return t.bootstrap == 2 ? u >= t.pois_cdf[0] : u < t.pois_cdf[0];
+}
+
 DML_HD uint64_t root_key(uint64_t seed) { return splitmix64(seed ^ 0x7EE5EEDull); }
 
 DML_HD uint64_t child_key(uint64_t parent, int side) {

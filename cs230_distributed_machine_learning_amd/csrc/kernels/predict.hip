@@ -53,16 +53,20 @@ static_assert(kTopLv >= 1 && kTopSlots <= 256, "ops/forest_ops.py TOP_SLOTS_MAX 
 // dependent node-load chains are independent, so U requests are in flight per thread
 // instead of one (tree traversal is latency-bound)
 // top (LDS, [kPredU][kTopSlots]) or nullptr: the group's top-level table (see kTopLv)
-template <int kPredU>
+// kMasked (the out-of-bag walk): slot u is walked only when bit u of `mask` is set -- a masked
+// slot starts as a leaf record and issues no load (its leaf[u] stays the root and is not read)
+template <int kPredU, bool kMasked = false>
 __device__ __forceinline__ void leaves_u(const NodeRec* __restrict__ nodes, const uint8_t* __restrict__ xr, int t0,
-                                         int u_n, int (&leaf)[kPredU], int cap, const NodeRec* top) {
+                                         int u_n, int (&leaf)[kPredU], int cap, const NodeRec* top,
+                                         uint32_t mask = ~0u) {
   NodeRec nr[kPredU];
   int sl[kPredU];
 #pragma unroll
   for (int u = 0; u < kPredU; ++u) {
     leaf[u] = t0 + u;
     sl[u] = 0;
-    nr[u] = u < u_n ? (top ? top[u * kTopSlots] : nodes[leaf[u]]) : NodeRec{-1, -1};
+    const bool walk = u < u_n && (!kMasked || ((mask >> u) & 1u));
+    nr[u] = walk ? (top ? top[u * kTopSlots] : nodes[leaf[u]]) : NodeRec{-1, -1};
   }
   for (int steps = 0; steps < cap; ++steps) {   // step s: every unfinished tree at depth s
     bool any = false;
@@ -275,6 +279,156 @@ __global__ __launch_bounds__(256) void k_predict_reg(PredictArgs a) {
   (GPTR(float, a.out_pred))[r0 + i] = nt ? (float)(acc / nt) : 0.f;
 }
 
+// ---- out-of-bag prediction of a kept fit ----------------------------------------------
+// The predict walk over the fit's TRAINING rows, where tree t takes part in row r's
+// average iff boot_weight(specs[t], r) == 0 (forest_common.h boot_is_oob: recomputed from
+// the tree seed and the row id, nothing stored).  Every thread of a block still walks the
+// same U consecutive trees (so the block-wide LDS top table works); the in-bag slots of a
+// lane are masked in leaves_u and load nothing.  ../runtime/forest_oob_cpu.cpp is the same
+// loop in the same order on the host: the outputs agree bit for bit.
+struct OobArgs {
+  int64_t Xb, ld, d;
+  int64_t nodes, node_val, VC, is_reg, n_classes;
+  int64_t specs;         // TreeSpec[] of the pool (indexed by pool tree id)
+  int64_t fit_tree_off;  // int32[2] device: the fit's pool trees [t0, t1)
+  int64_t fit_row_off;   // int64[2] device: {0, n_rows}
+  int64_t t0, t1;
+  int64_t rows, n_rows;  // int32[n_rows]: dataset row ids (the split's training rows, ascending)
+  int64_t depth_cap;     // <= 0: whole trees
+  int64_t out;           // float [n_rows][C] (classification) or [n_rows] (regression)
+  int64_t out_pred;      // int32 [n_rows] (classification): first maximum of the row's sums
+  int64_t out_cnt;       // int32 [n_rows]: trees that left the row out
+  int64_t toptab;        // NodeRec[t1][kTopSlots] scratch or 0
+};
+
+struct OobTail {   // what the OOB kernels take besides the predict block
+  const TreeSpec* specs;
+  int32_t* cnt;
+  int cap;
+};
+
+// bit u set: tree t + u (u < u_n) left the row out
+template <int kPredU>
+__device__ __forceinline__ uint32_t oob_mask(const TreeSpec* __restrict__ specs, int t, int u_n, uint64_t row_key) {
+  uint32_t m = 0;
+#pragma unroll
+  for (int u = 0; u < kPredU; ++u)
+    if (u < u_n && boot_is_oob(specs[t + u], row_key)) m |= 1u << u;   // specs[t + u]: wave-uniform address
+  return m;
+}
+
+template <int MAXC, int kPredU>
+__global__ __launch_bounds__(256) void k_oob_cls(PredictArgs a, OobTail e) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t xs_lds[];
+  const int32_t* toff = GPTR(const int32_t, a.fit_tree_off);
+  const int64_t* roff = GPTR(const int64_t, a.fit_row_off);
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t r0 = roff[0], nr = roff[1] - r0;
+  if ((int64_t)blockIdx.x * 256 >= nr) return;
+  const bool live = i < nr;
+  NodeRec* top = a.toptab ? (NodeRec*)(xs_lds + top_lds_off(a)) : nullptr;
+  const uint8_t* xr;
+  if (a.lds_pitch) {
+    xr = stage_rows(a, xs_lds, r0, nr);
+    if (!live && !top) return;
+  } else {
+    if (!live && !top) return;
+    xr = nullptr;
+  }
+  const int32_t row = (GPTR(const int32_t, a.rows))[r0 + (live ? i : 0)];
+  if (!a.lds_pitch) xr = GPTR(const uint8_t, a.Xb) + (int64_t)row * a.ld;
+  const uint64_t rk = boot_row_key((uint32_t)row);
+  const int C = (int)a.n_classes;
+  const NodeRec* nodes = GPTR(const NodeRec, a.nodes);
+  const double* val = GPTR(const double, a.node_val);
+  float p[MAXC];
+#pragma unroll
+  for (int k = 0; k < MAXC; ++k) p[k] = 0.f;
+  int cnt = 0;
+  const int tend = toff[1];
+  for (int t = toff[0]; t < tend; t += kPredU) {
+    int leaf[kPredU];
+    const int u_all = min(kPredU, tend - t), u_n = live ? u_all : 0;
+    if (top) load_top<kPredU>(a, top, t, u_all);
+    const uint32_t m = oob_mask<kPredU>(e.specs, t, u_n, rk);
+    leaves_u<kPredU, true>(nodes, xr, t, u_n, leaf, e.cap, top, m);
+    // accumulate in tree order (bit-identical to the host twin)
+#pragma unroll
+    for (int u = 0; u < kPredU; ++u) {
+      if (!((m >> u) & 1u)) continue;
+      ++cnt;
+      const double* v = val + (int64_t)leaf[u] * a.VC;
+      double W = 0.0;
+#pragma unroll
+      for (int k = 0; k < MAXC; ++k)
+        if (k < C) W += v[k];
+      if (W > 0.0) {
+        const double inv = 1.0 / W;
+#pragma unroll
+        for (int k = 0; k < MAXC; ++k)
+          if (k < C) p[k] += (float)(v[k] * inv);
+      }
+    }
+  }
+  if (!live) return;
+  int best = 0;
+  float bv = p[0];
+#pragma unroll
+  for (int k = 1; k < MAXC; ++k)
+    if (k < C && p[k] > bv) { bv = p[k]; best = k; }
+  (GPTR(int32_t, a.out_pred))[r0 + i] = best;
+  e.cnt[r0 + i] = cnt;
+  const float nt = (float)cnt;
+  float* op = GPTR(float, a.out_proba) + (r0 + i) * C;
+#pragma unroll
+  for (int k = 0; k < MAXC; ++k)
+    if (k < C) op[k] = cnt ? p[k] / nt : 0.f;
+}
+
+template <int kPredU>
+__global__ __launch_bounds__(256) void k_oob_reg(PredictArgs a, OobTail e) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t xs_lds[];
+  const int32_t* toff = GPTR(const int32_t, a.fit_tree_off);
+  const int64_t* roff = GPTR(const int64_t, a.fit_row_off);
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t r0 = roff[0], nr = roff[1] - r0;
+  if ((int64_t)blockIdx.x * 256 >= nr) return;
+  const bool live = i < nr;
+  NodeRec* top = a.toptab ? (NodeRec*)(xs_lds + top_lds_off(a)) : nullptr;
+  const uint8_t* xr;
+  if (a.lds_pitch) {
+    xr = stage_rows(a, xs_lds, r0, nr);
+    if (!live && !top) return;
+  } else {
+    if (!live && !top) return;
+    xr = nullptr;
+  }
+  const int32_t row = (GPTR(const int32_t, a.rows))[r0 + (live ? i : 0)];
+  if (!a.lds_pitch) xr = GPTR(const uint8_t, a.Xb) + (int64_t)row * a.ld;
+  const uint64_t rk = boot_row_key((uint32_t)row);
+  const NodeRec* nodes = GPTR(const NodeRec, a.nodes);
+  const double* val = GPTR(const double, a.node_val);
+  double acc = 0.0;
+  int cnt = 0;
+  const int tend = toff[1];
+  for (int t = toff[0]; t < tend; t += kPredU) {
+    int leaf[kPredU];
+    const int u_all = min(kPredU, tend - t), u_n = live ? u_all : 0;
+    if (top) load_top<kPredU>(a, top, t, u_all);
+    const uint32_t m = oob_mask<kPredU>(e.specs, t, u_n, rk);
+    leaves_u<kPredU, true>(nodes, xr, t, u_n, leaf, e.cap, top, m);
+#pragma unroll
+    for (int u = 0; u < kPredU; ++u) {
+      if (!((m >> u) & 1u)) continue;
+      const double* v = val + (int64_t)leaf[u] * a.VC;
+      if (v[0] > 0.0) { acc += v[1] / v[0]; ++cnt; }
+    }
+  }
+  if (!live) return;
+  (GPTR(float, a.out_pred))[r0 + i] = cnt ? (float)(acc / cnt) : 0.f;
+  e.cnt[r0 + i] = cnt;
+}
+
 // per-fit score statistics: out[f] = {match_count or SSE, sum y, sum y^2, n}
 struct ScoreArgs {
   int64_t rows;        // int32[] row ids
@@ -423,6 +577,45 @@ static int launch_predict(PredictArgs* a, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
+// one launch over the kept fit's training rows: launch_predict's LDS layout (staged rows, top
+// table of the U trees being walked) with F = 1
+template <int U>
+static int launch_oob(const OobArgs* o, hipStream_t st) {
+  PredictArgs a{};
+  a.Xb = o->Xb; a.ld = o->ld; a.d = o->d;
+  a.nodes = o->nodes; a.node_val = o->node_val; a.VC = o->VC; a.is_reg = o->is_reg; a.n_classes = o->n_classes;
+  a.fit_tree_off = o->fit_tree_off; a.fit_row_off = o->fit_row_off; a.rows = o->rows;
+  a.out_pred = o->is_reg ? o->out : o->out_pred;
+  a.out_proba = o->is_reg ? 0 : o->out;
+  a.F = 1; a.max_rows = o->n_rows; a.max_trees = o->t1 - o->t0;
+  a.toptab = o->toptab;
+  a.lds_pitch = predict_pitch(&a);
+  size_t lds = (size_t)a.lds_pitch * 256;
+  static const bool top_off = getenv("DML_PRED_NO_TOP") != nullptr;
+  const size_t lds_top = ((lds + 15) & ~(size_t)15) + (size_t)U * kTopSlots * sizeof(NodeRec);
+  if (top_off || lds_top > 64 * 1024) a.toptab = 0;
+  if (a.toptab) {
+    k_top_fill<<<dim3((unsigned)((a.max_trees + 3) / 4), 1), 256, 0, st>>>(a);
+    lds = lds_top;
+  }
+  const OobTail e{GPTR(const TreeSpec, o->specs), GPTR(int32_t, o->out_cnt),
+                  o->depth_cap > 0 ? (int)o->depth_cap : 1 << 20};
+  const dim3 grid((unsigned)((o->n_rows + 255) / 256), 1);
+  if (o->is_reg) {
+    k_oob_reg<U><<<grid, 256, lds, st>>>(a, e);
+  } else {
+    const int C = (int)o->n_classes;
+    if (C <= 2) k_oob_cls<2, U><<<grid, 256, lds, st>>>(a, e);
+    else if (C <= 4) k_oob_cls<4, U><<<grid, 256, lds, st>>>(a, e);
+    else if (C <= 8) k_oob_cls<8, U><<<grid, 256, lds, st>>>(a, e);
+    else if (C <= 16) k_oob_cls<16, U><<<grid, 256, lds, st>>>(a, e);
+    else if (C <= 32) k_oob_cls<32, U><<<grid, 256, lds, st>>>(a, e);
+    else if (C <= 64) k_oob_cls<64, U><<<grid, 256, lds, st>>>(a, e);
+    else return 5;
+  }
+  return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
 // max_leaf_nodes: one lane per limited tree replays sklearn's best-first order over the
 // grown tree (forest_common.h best_first_prune); the frontier heap lives in global
 // scratch, ``cap`` entries per lane.  Trees with limit 0 are left alone.
@@ -498,6 +691,18 @@ int dml_forest_predict_fit(const PredictArgs* a, int32_t f, hipStream_t st) {
   if (a->fit_depth_cap) b.fit_depth_cap = a->fit_depth_cap + 4 * (int64_t)f;
   b.max_rows = roff ? roff[f + 1] - roff[f] : a->max_rows;
   return dml_forest_predict(&b, st);
+}
+
+int dml_oob_sizeof_args() { return (int)sizeof(OobArgs); }
+
+// out-of-bag prediction of one kept fit over its training rows (k_oob_cls / k_oob_reg)
+int dml_forest_oob(const OobArgs* o, hipStream_t st) {
+  if (o->n_rows <= 0) return 0;
+  if (o->t1 <= o->t0 || o->t0 < 0) return 2;
+  static const int u = [] { const char* e = getenv("DML_PRED_U"); return e ? atoi(e) : 8; }();
+  if (u == 16) return launch_oob<16>(o, st);
+  if (u == 4) return launch_oob<4>(o, st);
+  return launch_oob<8>(o, st);
 }
 
 int dml_scores(ScoreArgs* a, hipStream_t st) {

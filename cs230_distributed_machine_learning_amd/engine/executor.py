@@ -247,6 +247,11 @@ def run_candidates(data, spec: JobSpec, candidate_ids: Sequence[int]) -> List[Ca
                     R["mean_squared_error"] = -_scores_for(data, t, o, "neg_mean_squared_error")
                 R["training_time"] = o.fit_seconds
                 model = o.model
+                if isinstance(model, dict) and model.get("oob_score") is not None:   # RandomForest* oob_score=True
+                    R["oob_score"] = float(model["oob_score"])
+                    for w in o.info.get("warnings", []):   # the kept fit's own (rows no tree left out)
+                        if w not in warnings:
+                            warnings.append(w)
             else:
                 R["training_time"] = fit_s
             if cv_idx:

@@ -27,7 +27,8 @@ from typing import Any, Dict, Optional
 import numpy as np
 
 _ARRAY_KEYS = ("nodes", "vals", "edges", "coef", "intercept", "X", "y", "init", "stage_offsets", "scale", "mean",
-               "components", "var", "min", "max", "value", "roots")
+               "components", "var", "min", "max", "value", "roots", "feature_importances", "oob_rows",
+               "oob_decision_function", "oob_prediction")
 
 
 def save_model(model: Dict[str, Any], path: str) -> str:
@@ -260,6 +261,54 @@ class Predictor:
             if svm_has_proba(self.model):   # fitted with probability=True: probA / probB per machine
                 return svm_proba_numpy(self.model, X)
         raise AttributeError(f"{self.model_type} has no predict_proba (sklearn's default probability=False)")
+
+    # ---- fitted forest attributes (sklearn's names; AttributeError when the artefact lacks one) ----
+    @property
+    def feature_importances_(self) -> np.ndarray:
+        """Mean decrease in impurity (ops/forest_ops.py ``feature_importances``).  A forest
+        artefact saved without the vector computes it from its nodes and node sums."""
+        if self.kind != "forest":
+            raise AttributeError(f"{self.model_type} artefact has no feature_importances_")
+        fi = self.model.get("feature_importances")
+        if fi is None:
+            from ..ops import forest_ops
+
+            crit = self.model.get("params", {}).get("criterion")
+            if crit in (forest_ops.POISSON, forest_ops.MAE):
+                name = "poisson" if crit == forest_ops.POISSON else "absolute_error"
+                raise AttributeError(f"feature_importances_ is not available for criterion={name!r}: the artefact "
+                                     f"does not hold that impurity's node sums")
+            if crit is None:
+                crit = forest_ops.MSE if self.model["is_reg"] else forest_ops.GINI
+            fi = forest_ops.feature_importances(np.asarray(self.model["nodes"]), np.asarray(self.model["vals"]),
+                                                int(self.model["n_trees"]), int(self.model["n_features"]),
+                                                bool(self.model["is_reg"]), int(crit))
+            self.model["feature_importances"] = fi
+        return np.asarray(fi, dtype=np.float64)
+
+    def _oob(self, key: str, name: str):
+        v = self.model.get(key) if self.kind == "forest" else None
+        if v is None:
+            raise AttributeError(f"{self.model_type} artefact has no {name} (fit with oob_score=True, bootstrap=True)")
+        return v
+
+    @property
+    def oob_score_(self) -> float:
+        return float(self._oob("oob_score", "oob_score_"))
+
+    @property
+    def oob_decision_function_(self) -> np.ndarray:
+        """[len(oob_rows_), n_classes] in ``classes_`` order; rows no tree left out are zeros."""
+        return np.asarray(self._oob("oob_decision_function", "oob_decision_function_"))
+
+    @property
+    def oob_prediction_(self) -> np.ndarray:
+        return np.asarray(self._oob("oob_prediction", "oob_prediction_"))
+
+    @property
+    def oob_rows_(self) -> np.ndarray:
+        """Dataset row ids the out-of-bag arrays are aligned with (the fit's training rows)."""
+        return np.asarray(self._oob("oob_rows", "oob_rows_"))
 
     # ---- transformers ------------------------------------------------------------------
     def transform(self, X) -> np.ndarray:

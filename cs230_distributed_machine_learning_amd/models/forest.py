@@ -12,8 +12,13 @@ absolute_error: exact weighted medians, on its own GPU builder), max_depth,
 min_samples_split, min_samples_leaf (int or fraction), max_features (sqrt/log2/None/
 int/float), bootstrap, max_samples, min_impurity_decrease, max_leaf_nodes (sklearn's
 best-first tree: the grown tree is cut to its best-first top, ops/forest_ops.py
-prune_max_leaves), random_state.  Parameters
-with no effect on the fitted function (n_jobs, verbose, warm_start, oob_score) are
+prune_max_leaves), random_state, oob_score (bool; kept models only: the out-of-bag walk of
+ops/forest_ops.py oob_predict over the fit's training rows gives oob_score,
+oob_decision_function / oob_prediction and oob_rows; CV fits do no extra work; not computed
+for row-sharded jobs).  Every kept model also carries sklearn's feature_importances (mean
+decrease in impurity from the pool's node sums, forest_ops.feature_importances; not for
+criterion poisson / absolute_error, whose impurities the pool does not hold).  Parameters
+with no effect on the fitted function (n_jobs, verbose, warm_start) are
 accepted and ignored; class_weight (dict / "balanced" / "balanced_subsample") scales
 the per-class sums inside the builder exactly where sklearn's sample weights would;
 ccp_alpha > 0 prunes every grown tree to its minimal cost-complexity subtree
@@ -137,6 +142,9 @@ class ForestFamily(Family):
                     raise ParamError("max_samples fraction must be in (0, 1]")
             else:
                 lam = min(1.0, as_int(ms, "max_samples", lo=1) / max(1, n_train))
+        oob = as_bool(p["oob_score"], "oob_score")   # sklearn's callable scorer is not supported: a ParamError
+        if oob and not boot:
+            raise ParamError("Out of bag estimation only available if bootstrap=True")
         mid = as_float(p["min_impurity_decrease"], "min_impurity_decrease", lo=0.0)
         cw = p["class_weight"]
         if cw in ("None",):
@@ -181,7 +189,7 @@ class ForestFamily(Family):
             "min_samples_split": mss, "min_samples_leaf": msl, "max_features": k, "bootstrap": int(boot),
             "lambda": lam, "min_impurity_decrease": mid, "seed": seed_of(p["random_state"]), "warnings": warn,
             "class_weight": cw, "max_leaf_nodes": mln or 0, "ccp_alpha": ccp, "min_weight_fraction_leaf": mwf,
-            "monotonic_cst": mono,
+            "monotonic_cst": mono, "oob_score": oob,
         }
 
     def cost(self, model_type, rp, n_train, n_features, n_classes) -> float:
@@ -288,6 +296,9 @@ class ForestFamily(Family):
                 if t.params.get("criterion") == forest_ops.MAE or t.params.get("monotonic_cst") is not None:
                     raise ParamError("criterion='absolute_error' and monotonic_cst need every row on one rank: "
                                      "run this job with parallelism='task'")
+                msg = "oob_score is not computed for row-sharded jobs (run with parallelism='task')"
+                if t.params.get("oob_score") and msg not in t.params["warnings"]:
+                    t.params["warnings"] = t.params["warnings"] + [msg]
         # absolute_error trees grow on their own builder (forest_mae.hip / forest_cpu.cpp): batch them apart
         tasks_in = tasks
         # fits differing only in n_estimators with an explicit random_state grow the same first
@@ -531,6 +542,7 @@ class ForestFamily(Family):
                               info={"warnings": t.params.get("warnings", []), "batch_stats": dict(fb.stats)})
                 if keep_models and t.keep:
                     o.model = extract_forest(fb, int(toff[f]), int(toff[f + 1]), data, t)
+                    self._attach_oob(data, Xb, fb, specs, o, int(toff[f]), int(toff[f + 1]), t, 0)
                 outs.append(o)
                 for fo in (follow or {}).get(t.task_id, []):   # prefix fits: leader f's first m trees
                     m = int(fo.params["n_estimators"])
@@ -551,10 +563,34 @@ class ForestFamily(Family):
                                          "prefix_of": t.task_id})
                     if keep_models and fo.keep:
                         of.model = extract_forest(fb, int(toff[f]), int(toff[f]) + m, data, fo, depth_cap=cap)
+                        self._attach_oob(data, Xb, fb, specs, of, int(toff[f]), int(toff[f]) + m, fo, cap)
                     outs.append(of)
             return outs
         finally:   # the node pool is an arena slot: free it for the next batch
             forest_ops.release_pool(fb)
+
+    def _attach_oob(self, data, Xb, fb, specs: np.ndarray, out: FitOutput, t0: int, t1: int, task: FitTask,
+                    cap: int) -> None:
+        """oob_score=True on a kept fit: the out-of-bag walk of pool trees [t0, t1) over the fit's
+        training rows (forest_ops.oob_predict), attached to the model ``extract_forest`` returned.
+        A fit without oob_score launches and allocates nothing."""
+        if not task.params.get("oob_score") or getattr(data, "is_row_shard", False):   # run() warned a sharded job
+            return
+        rows = data.train_rows[task.split]
+        is_reg = bool(fb.is_reg)
+        res = forest_ops.oob_predict(fb, Xb if fb.on_gpu else Xb.numpy(), specs, t0, t1,
+                                     rows if fb.on_gpu else rows.numpy(), depth_cap=cap)
+        dec, cnt = res[0], res[1]
+        score = forest_ops.oob_score(rows if fb.on_gpu else rows.numpy(), dec if is_reg else res[2],
+                                     ycls=data.y_cls, yreg=data.y_reg, is_reg=is_reg)
+        if bool((cnt == 0).any()):   # sklearn >= 1.0 warns and leaves such rows at zero
+            out.info["warnings"] = list(out.info.get("warnings", [])) + [
+                "Some inputs do not have OOB scores. This probably means too few trees were used to compute "
+                "any reliable OOB estimates."]
+        to_np = lambda a: a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        out.model["oob_score"] = float(score)
+        out.model["oob_rows"] = to_np(rows).astype(np.int32)
+        out.model["oob_prediction" if is_reg else "oob_decision_function"] = to_np(dec).astype(np.float32)
 
 
 def _early_ok(data, batch: List[FitTask], is_reg: bool, mono) -> bool:
@@ -643,9 +679,18 @@ def extract_forest(fb, t0: int, t1: int, data, task: FitTask, depth_cap: int = 0
         fo = torch.stack([l_old, l_old + 1], 1).reshape(-1)   # children pairs stay adjacent
         nxt += 2 * k
     old = torch.cat(order)
-    nn = torch.stack([torch.cat(splits), torch.cat(lefts)], 1).cpu().numpy().astype(np.int32)
-    vv = vals[old].cpu().numpy().astype(np.float64)
+    nn_dev, vv_dev = torch.stack([torch.cat(splits), torch.cat(lefts)], 1), vals[old]
+    nn = nn_dev.cpu().numpy().astype(np.int32)
+    vv = vv_dev.cpu().numpy().astype(np.float64)
+    # sklearn's feature_importances_ of the extracted trees (depth caps and pruned nodes are
+    # leaves by now); poisson / absolute_error impurities are not in the pool: no importances
+    crit = task.params.get("criterion")
+    extra = {}
+    if crit in (forest_ops.GINI, forest_ops.ENTROPY, forest_ops.MSE, forest_ops.FRIEDMAN):
+        extra["feature_importances"] = forest_ops.feature_importances(nn_dev, vv_dev, T, int(data.d), bool(fb.is_reg),
+                                                                      int(crit))
     return {
+        **extra,
         "kind": "forest",
         "is_reg": bool(fb.is_reg),
         "n_classes": int(fb.n_classes),

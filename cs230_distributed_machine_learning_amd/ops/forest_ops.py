@@ -880,6 +880,130 @@ def apply(fb: ForestBuild, Xb, t0: int = 0, T: Optional[int] = None):
     return leaf
 
 
+def oob_predict(fb: ForestBuild, Xb, specs: np.ndarray, t0: int, t1: int, rows, depth_cap: int = 0):
+    """Out-of-bag prediction of pool trees [t0, t1) over ``rows`` (the fit's training rows,
+    ascending dataset row ids): tree t takes part in row r's average iff its bootstrap weight
+    of r is 0 (forest_common.h ``boot_is_oob``; recomputed from the tree seed, nothing is
+    stored).  GPU pool: predict.hip ``k_oob_cls`` / ``k_oob_reg``; host pool: its twin,
+    csrc/runtime/forest_oob_cpu.cpp -- bit-equal outputs.  ``depth_cap`` > 0 reads the trees
+    down to that depth (a max_depth prefix fit).  Returns, on the pool's device,
+    ``(out float32 [n, C], cnt int32 [n], pred int32 [n])`` for classification (``out`` the mean
+    leaf class fractions over the row's ``cnt`` out-of-bag trees, zeros where ``cnt == 0``) or
+    ``(out float32 [n], cnt)`` for regression."""
+    C = int(fb.n_classes)
+    specs = np.ascontiguousarray(specs)
+    if not 0 <= t0 < t1 <= len(specs):
+        raise ValueError(f"oob_predict: trees [{t0}, {t1}) outside the pool's {len(specs)} specs")
+    if fb.on_gpu:
+        dev = fb.nodes.device
+        rows_t = rows if isinstance(rows, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int32))
+        rows_t = rows_t.to(dev, dtype=torch.int32).contiguous()
+        n = int(rows_t.numel())
+        specs_dev = torch.from_numpy(specs.view(np.uint8).copy()).to(dev)
+        toff = torch.tensor([t0, t1], dtype=torch.int32).to(dev)
+        roff = torch.tensor([0, n], dtype=torch.int64).to(dev)
+        out = torch.empty(n if fb.is_reg else (n, C), dtype=torch.float32, device=dev)
+        cnt = torch.empty(n, dtype=torch.int32, device=dev)
+        pred = None if fb.is_reg else torch.empty(n, dtype=torch.int32, device=dev)
+        top = torch.empty((int(t1) * TOP_SLOTS_MAX, 2), dtype=torch.int32, device=dev)   # indexed by pool tree id
+        o = native.OobArgs()
+        o.Xb, o.ld, o.d = native.ptr(Xb), Xb.stride(0), int(Xb.shape[1])
+        o.nodes, o.node_val, o.VC = native.ptr(fb.nodes), native.ptr(fb.vals), int(fb.VC)
+        o.is_reg, o.n_classes, o.specs = int(fb.is_reg), C, native.ptr(specs_dev)
+        o.fit_tree_off, o.fit_row_off, o.t0, o.t1 = native.ptr(toff), native.ptr(roff), int(t0), int(t1)
+        o.rows, o.n_rows, o.depth_cap = native.ptr(rows_t), n, int(depth_cap)
+        o.out, o.out_pred, o.out_cnt, o.toptab = native.ptr(out), native.ptr(pred), native.ptr(cnt), native.ptr(top)
+        with trace.range("forest_oob"):
+            rc = native.hip_lib().dml_forest_oob(ctypes.byref(o), native.stream_handle(dev))
+        if rc:
+            raise RuntimeError(f"dml_forest_oob failed ({rc})")
+        torch.cuda.current_stream(dev).synchronize()   # keep specs_dev / top / offsets alive until done
+        return (out, cnt) if fb.is_reg else (out, cnt, pred)
+    Xb = np.ascontiguousarray(Xb)
+    rows_np = np.ascontiguousarray(rows.cpu().numpy() if isinstance(rows, torch.Tensor) else rows, dtype=np.int32)
+    n = len(rows_np)
+    nodes = np.ascontiguousarray(fb.nodes, dtype=np.int32)
+    vals = np.ascontiguousarray(fb.vals, dtype=np.float64)
+    out = np.empty(n if fb.is_reg else (n, C), dtype=np.float32)
+    cnt = np.empty(n, dtype=np.int32)
+    pred = None if fb.is_reg else np.empty(n, dtype=np.int32)
+    native.cpu_lib().dml_cpu_forest_oob(native.ptr(Xb), Xb.shape[1], native.ptr(nodes), native.ptr(vals), int(fb.VC),
+                                        int(fb.is_reg), C, native.ptr(specs), int(t0), int(t1), native.ptr(rows_np), n,
+                                        int(depth_cap), native.ptr(out), native.ptr(pred), native.ptr(cnt))
+    return (out, cnt) if fb.is_reg else (out, cnt, pred)
+
+
+def oob_score(rows, pred, ycls=None, yreg=None, is_reg: bool = False) -> float:
+    """sklearn's ``oob_score_`` from an out-of-bag prediction (``oob_predict``'s ``pred`` for a
+    classifier, ``out`` for a regressor) over ``rows``: accuracy, or R^2 = 1 - SSE /
+    (sum y^2 - (sum y)^2 / n), in float64 from ``score_stats``' sums."""
+    n = int(rows.numel() if isinstance(rows, torch.Tensor) else len(rows))
+    if n == 0:
+        return float("nan")
+    s = score_stats(rows, np.array([0, n], dtype=np.int64), pred, ycls=ycls, yreg=yreg, is_reg=is_reg)[0]
+    if not is_reg:
+        return float(s[0]) / n
+    ss_tot = float(s[2]) - float(s[1]) * float(s[1]) / n
+    if ss_tot <= 0.0:   # constant target (search/scoring.py "r2")
+        return 1.0 if float(s[0]) == 0.0 else 0.0
+    return 1.0 - float(s[0]) / ss_tot
+
+
+def feature_importances(nodes, vals, n_trees: int, d: int, is_reg: bool, criterion: int) -> np.ndarray:
+    """sklearn's ``feature_importances_`` (mean decrease in impurity) of trees rooted at nodes
+    0 .. n_trees-1 of a pool: float64 [d].
+
+    Per internal node ``(W_t imp_t - W_l imp_l - W_r imp_r) / W_root`` goes to the node's
+    feature; each tree is normalised to sum 1, the mean is taken over the trees with more
+    than one node and normalised again (all zeros when every tree is a single leaf).  The
+    impurities come from ``vals`` as ``prune_ccp`` computes them (gini, entropy in log2,
+    sum wy^2 / W - mean^2 for squared_error / friedman_mse), so bootstrap and class weights
+    are in.  Works on either device, one vectorised step per tree level (no per-node host
+    loop).  ``poisson`` / ``absolute_error``: the pool does not hold their impurities."""
+    if criterion not in (GINI, ENTROPY, MSE, FRIEDMAN):
+        raise ValueError("feature importances need the gini, entropy, squared_error or friedman_mse impurity")
+    nodes = torch.from_numpy(np.ascontiguousarray(nodes)) if not isinstance(nodes, torch.Tensor) else nodes
+    vals = torch.from_numpy(np.ascontiguousarray(vals)) if not isinstance(vals, torch.Tensor) else vals
+    dev = nodes.device
+    T = int(n_trees)
+    v = vals.double()
+    if is_reg:
+        w = v[:, 0]
+        m = v[:, 1] / w.clamp_min(1e-300)
+        imp = torch.where(w > 0, v[:, 2] / w.clamp_min(1e-300) - m * m, torch.zeros_like(w))
+    else:
+        w = v.sum(1)
+        p = v / w.clamp_min(1e-300).unsqueeze(1)
+        if criterion == ENTROPY:
+            imp = -(torch.where(p > 0, p * torch.log2(p.clamp_min(1e-300)), torch.zeros_like(p))).sum(1)
+        else:
+            imp = 1.0 - (p * p).sum(1)
+        del p
+    wi = w * imp
+    del imp, v
+    acc = torch.zeros(T * d, dtype=torch.float64, device=dev)
+    fo = torch.arange(T, dtype=torch.int64, device=dev)
+    tr = fo.clone()
+    while fo.numel():
+        rec = nodes[fo]
+        internal = rec[:, 0] >= 0
+        fi, tr = fo[internal], tr[internal]
+        l = rec[internal, 1].to(torch.int64)
+        feat = rec[internal, 0].to(torch.int64) >> 8
+        acc.index_add_(0, tr * d + feat, (wi[fi] - wi[l] - wi[l + 1]) / w[tr])   # w[tr]: the tree's root weight
+        tr = tr.repeat_interleave(2)
+        fo = torch.stack([l, l + 1], 1).reshape(-1)
+    per = acc.view(T, d)
+    s = per.sum(1, keepdim=True)
+    per = torch.where(s > 0, per / s.clamp_min(1e-300), per)
+    multi = nodes[:T, 0] >= 0   # trees with more than one node
+    if not bool(multi.any()):
+        return np.zeros(d, dtype=np.float64)
+    mean = per[multi].sum(0) / int(multi.sum())
+    tot = float(mean.sum())
+    return (mean / tot if tot > 0 else mean).cpu().numpy()
+
+
 class GpuPredict:
     """A GPU predict of F fits set up before (or after) their build: device offset arrays,
     output buffers and the ``PredictArgs`` block.  ``run(fits)`` predicts a subset of the

@@ -88,6 +88,13 @@ PredictArgs = _i64_struct(
 
 ScoreArgs = _i64_struct("ScoreArgs", ["rows", "fit_row_off", "pred", "ycls", "yreg", "is_reg", "out", "F"])
 
+# csrc/kernels/predict.hip OobArgs (out-of-bag prediction of one kept fit)
+OobArgs = _i64_struct(
+    "OobArgs",
+    ["Xb", "ld", "d", "nodes", "node_val", "VC", "is_reg", "n_classes", "specs", "fit_tree_off", "fit_row_off",
+     "t0", "t1", "rows", "n_rows", "depth_cap", "out", "out_pred", "out_cnt", "toptab"],
+)
+
 # csrc/kernels/lr_mfma.hip argument blocks (MFMA logistic-regression objective)
 LrFwdArgs = _i64_struct(
     "LrFwdArgs",
@@ -146,6 +153,9 @@ def cpu_lib() -> ctypes.CDLL:
             lib.dml_cpu_forest_free.argtypes = [c_vp]
             lib.dml_cpu_forest_predict.argtypes = [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp,
                                                    c_i64, c_vp, c_vp, c_vp]
+            lib.dml_cpu_forest_oob.argtypes = [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_i32, c_vp,
+                                               c_i64, c_i32, c_vp, c_vp, c_vp]
+            lib.dml_boot_weight_oob.argtypes = [c_vp, ctypes.c_uint32, c_vp]
             lib.dml_cpu_bin.argtypes = [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64]
             lib.dml_cpu_svm_sizeof_prob.restype = c_i32
             lib.dml_cpu_svm_smo.argtypes = [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]
@@ -194,6 +204,11 @@ def hip_lib() -> ctypes.CDLL:
             lib.dml_forest_predict_fit.argtypes = [ctypes.POINTER(PredictArgs), c_i32, c_vp]
             lib.dml_scores.restype = c_i32
             lib.dml_scores.argtypes = [ctypes.POINTER(ScoreArgs), c_vp]
+            lib.dml_oob_sizeof_args.restype = c_i32
+            if lib.dml_oob_sizeof_args() != ctypes.sizeof(OobArgs):
+                raise RuntimeError("OobArgs layout mismatch between HIP library and Python")
+            lib.dml_forest_oob.restype = c_i32
+            lib.dml_forest_oob.argtypes = [ctypes.POINTER(OobArgs), c_vp]
             lib.dml_bin.restype = c_i32
             lib.dml_bin.argtypes = [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp]
             _register_optional(lib)
