@@ -429,6 +429,340 @@ __global__ __launch_bounds__(256) void k_oob_reg(PredictArgs a, OobTail e) {
   e.cnt[r0 + i] = cnt;
 }
 
+// ---- permutation importance of a kept fit on its held-out rows ------------------------------
+// For feature f (grid.y, from features[]) and repeat k, row i is predicted from its own bins
+// except that feature f's bin comes from row rows[perm[k][i]]; the score statistic of every
+// (f, k) is reduced per block.  The prediction rule is k_predict_cls / k_predict_reg's (trees
+// ascending, the same float / double sums), so a tree whose leaf does not change adds the same
+// value: per group of U trees the baseline is walked once, recording for each slot whether a
+// visited node splits on f (`hit`), and a repeat walks again only the hit slots of a row whose
+// substituted bin differs from its own.  features[] may hold -1 (no node splits on it): that
+// slot's statistics are the baseline's.  ../runtime/forest_perm_cpu.cpp is the host twin.
+struct PermArgs {
+  int64_t Xb, ld, d;
+  int64_t nodes, node_val, VC, is_reg, n_classes;
+  int64_t fit_tree_off;  // int32[2] device: the fit's pool trees [t0, t1)
+  int64_t fit_row_off;   // int64[2] device: {0, n_rows}
+  int64_t t0, t1;
+  int64_t rows, n_rows;  // int32[n_rows]: dataset row ids (the split's held-out rows, ascending)
+  int64_t depth_cap;     // <= 0: whole trees
+  int64_t perm, K;       // int32 [K][n_rows]: positions in rows[]
+  int64_t features, F;   // int32 [F]: feature ids, or -1
+  int64_t ycls, yreg;    // targets by dataset row id: int32 (classification) / float (regression)
+  int64_t part;          // scratch [blocks][F][K]: int64 match counts / double squared errors
+  int64_t out;           // [F][K]: the block partials summed in block order
+  int64_t out_pred;      // optional [F][K][n_rows]: int32 class / float prediction
+  int64_t out_walked;    // optional uint64 [F]: (row, tree, repeat) slots walked a second time
+  int64_t toptab;        // NodeRec[t1][kTopSlots] scratch or 0
+  int64_t no_skip;       // A/B: walk every tree again for every repeat
+};
+
+struct PermTail {   // what the permutation kernels take besides the predict block
+  const int32_t* perm;
+  const int32_t* features;
+  const void* y;
+  void* part;
+  void* pred;
+  unsigned long long* walked;
+  int K, F, cap, no_skip;
+};
+
+// repeats whose accumulators a thread holds at once (K_chunk x MAXC floats stay in registers)
+constexpr int perm_chunk(int maxc) { return maxc <= 4 ? 8 : maxc <= 8 ? 4 : maxc <= 16 ? 2 : 1; }
+
+// leaves_u's masked walk for the permutation kernels.  kRecord: the baseline walk, which sets bit
+// u of `hit` when a visited node of slot u splits on feature f.  Otherwise feature f's bin is
+// `sub` (substituted in the compare: the rows may not be staged, and a staged byte stays as it is).
+template <int kPredU, bool kRecord>
+__device__ __forceinline__ void leaves_perm_u(const NodeRec* __restrict__ nodes, const uint8_t* __restrict__ xr, int t0,
+                                              int u_n, int (&leaf)[kPredU], int cap, const NodeRec* top, uint32_t mask,
+                                              int f, int sub, uint32_t& hit) {
+  NodeRec nr[kPredU];
+  int sl[kPredU];
+#pragma unroll
+  for (int u = 0; u < kPredU; ++u) {
+    leaf[u] = t0 + u;
+    sl[u] = 0;
+    const bool walk = u < u_n && ((mask >> u) & 1u);
+    nr[u] = walk ? (top ? top[u * kTopSlots] : nodes[leaf[u]]) : NodeRec{-1, -1};
+  }
+  for (int steps = 0; steps < cap; ++steps) {
+    bool any = false;
+#pragma unroll
+    for (int u = 0; u < kPredU; ++u) any |= nr[u].split >= 0;
+    if (!any) break;
+    const bool in_top = top && steps + 1 < kTopLv;
+#pragma unroll
+    for (int u = 0; u < kPredU; ++u) {
+      if (nr[u].split >= 0) {
+        const int feat = nr[u].split >> 8;
+        int bin = xr[feat];
+        if (kRecord) {
+          if (feat == f) hit |= 1u << u;
+        } else if (feat == f) {
+          bin = sub;
+        }
+        const int b = bin > (nr[u].split & 255) ? 1 : 0;
+        leaf[u] = nr[u].left + b;
+        if (in_top) {
+          sl[u] = 2 * sl[u] + 1 + b;
+          nr[u] = top[u * kTopSlots + sl[u]];
+        } else {
+          nr[u] = nodes[leaf[u]];
+        }
+      }
+    }
+  }
+}
+
+// the substituted bins of one row for repeats [k0, k0 + KC): feature f of row rows[perm[k][i]]
+template <int KC>
+__device__ __forceinline__ void perm_subs(const PredictArgs& a, const PermTail& e, int64_t i, int64_t nr, int f, int own,
+                                          bool live, int k0, int (&sub)[KC]) {
+#pragma unroll
+  for (int kk = 0; kk < KC; ++kk) {
+    sub[kk] = own;
+    if (live && f >= 0 && k0 + kk < e.K) {
+      const int32_t j = e.perm[(int64_t)(k0 + kk) * nr + i];
+      sub[kk] = (GPTR(const uint8_t, a.Xb))[(int64_t)(GPTR(const int32_t, a.rows))[j] * a.ld + f];
+    }
+  }
+}
+
+// block sum of one value per thread for each repeat of a chunk, in a fixed order (lanes by
+// xor-shuffle, then the four waves ascending) -> part[block][f][k]
+template <class T, int KC>
+__device__ __forceinline__ void perm_block_sums(const PermTail& e, T (&v)[KC], T (*red)[KC], int k0) {
+  const int w = threadIdx.x >> 6;
+#pragma unroll
+  for (int kk = 0; kk < KC; ++kk) {
+    T s = v[kk];
+    for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+    if ((threadIdx.x & 63) == 0) red[w][kk] = s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < KC && k0 + (int)threadIdx.x < e.K) {
+    const int kk = threadIdx.x;
+    ((T*)e.part)[((int64_t)blockIdx.x * e.F + blockIdx.y) * e.K + k0 + kk] =
+        red[0][kk] + red[1][kk] + red[2][kk] + red[3][kk];
+  }
+  __syncthreads();   // red is free for the next chunk
+}
+
+__device__ __forceinline__ void perm_count_walked(const PermTail& e, int nw) {
+  if (!e.walked) return;
+  for (int off = 32; off >= 1; off >>= 1) nw += __shfl_xor(nw, off);
+  if ((threadIdx.x & 63) == 0 && nw) atomicAdd(e.walked + blockIdx.y, (unsigned long long)nw);
+}
+
+template <int MAXC, int kPredU>
+__global__ __launch_bounds__(256) void k_perm_cls(PredictArgs a, PermTail e) {
+  constexpr int KC = perm_chunk(MAXC);
+  extern __shared__ __attribute__((aligned(16))) uint8_t xs_lds[];
+  __shared__ long long red[4][KC];
+  const int32_t* toff = GPTR(const int32_t, a.fit_tree_off);
+  const int64_t* roff = GPTR(const int64_t, a.fit_row_off);
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t r0 = roff[0], nr = roff[1] - r0;
+  if ((int64_t)blockIdx.x * 256 >= nr) return;
+  // every thread of a block with rows stays to the end (block-wide table loads and sums); a
+  // thread past the rows walks nothing and adds nothing
+  const bool live = i < nr;
+  NodeRec* top = a.toptab ? (NodeRec*)(xs_lds + top_lds_off(a)) : nullptr;
+  const uint8_t* xr = a.lds_pitch ? stage_rows(a, xs_lds, r0, nr) : nullptr;
+  const int32_t row = (GPTR(const int32_t, a.rows))[r0 + (live ? i : 0)];
+  if (!a.lds_pitch) xr = GPTR(const uint8_t, a.Xb) + (int64_t)row * a.ld;
+  const int f = e.features[blockIdx.y];
+  const int own = f >= 0 ? xr[f] : 0;
+  const int32_t label = ((const int32_t*)e.y)[row];
+  const int C = (int)a.n_classes;
+  const NodeRec* nodes = GPTR(const NodeRec, a.nodes);
+  const double* val = GPTR(const double, a.node_val);
+  const int tend = toff[1];
+  int nw = 0;
+  for (int k0 = 0; k0 < e.K; k0 += KC) {
+    int sub[KC];
+    perm_subs<KC>(a, e, i, nr, f, own, live, k0, sub);
+    float p[KC][MAXC];
+#pragma unroll
+    for (int kk = 0; kk < KC; ++kk)
+#pragma unroll
+      for (int k = 0; k < MAXC; ++k) p[kk][k] = 0.f;
+    for (int t = toff[0]; t < tend; t += kPredU) {
+      int base[kPredU];
+      const int u_all = min(kPredU, tend - t), u_n = live ? u_all : 0;
+      if (top) load_top<kPredU>(a, top, t, u_all);
+      uint32_t hit = 0;
+      leaves_perm_u<kPredU, true>(nodes, xr, t, u_n, base, e.cap, top, ~0u, f, 0, hit);
+      if (e.no_skip) hit = (1u << u_n) - 1u;
+      // narrow class counts: the baseline leaves' fractions are computed once per group and
+      // added as they are for every repeat that keeps the leaf (the same floats, so the same sums)
+      constexpr bool kKeep = MAXC <= 4;
+      float bc[kKeep ? kPredU : 1][MAXC];
+      uint32_t bok = 0;
+      if (kKeep) {
+#pragma unroll
+        for (int u = 0; u < kPredU; ++u) {
+          if (u >= u_n) continue;
+          const double* v = val + (int64_t)base[u] * a.VC;
+          double W = 0.0;
+#pragma unroll
+          for (int k = 0; k < MAXC; ++k)
+            if (k < C) W += v[k];
+          if (W > 0.0) {
+            const double inv = 1.0 / W;
+            bok |= 1u << u;
+#pragma unroll
+            for (int k = 0; k < MAXC; ++k)
+              if (k < C) bc[kKeep ? u : 0][k] = (float)(v[k] * inv);
+          }
+        }
+      }
+#pragma unroll
+      for (int kk = 0; kk < KC; ++kk) {
+        if (k0 + kk >= e.K) break;
+        int lk[kPredU];
+        const uint32_t m = (sub[kk] != own || e.no_skip) ? hit : 0u;
+        if (m) {
+          uint32_t none = 0;
+          leaves_perm_u<kPredU, false>(nodes, xr, t, u_n, lk, e.cap, top, m, f, sub[kk], none);
+          nw += __popc(m);
+        }
+        // accumulate in tree order (bit-identical to the predict kernels and the host twin)
+#pragma unroll
+        for (int u = 0; u < kPredU; ++u) {   // no break: a constant trip count keeps lk / base in registers
+          if (u >= u_n) continue;
+          if (kKeep && !((m >> u) & 1u)) {
+            if ((bok >> u) & 1u) {
+#pragma unroll
+              for (int k = 0; k < MAXC; ++k)
+                if (k < C) p[kk][k] += bc[kKeep ? u : 0][k];
+            }
+            continue;
+          }
+          const double* v = val + (int64_t)(((m >> u) & 1u) ? lk[u] : base[u]) * a.VC;
+          double W = 0.0;
+#pragma unroll
+          for (int k = 0; k < MAXC; ++k)
+            if (k < C) W += v[k];
+          if (W > 0.0) {
+            const double inv = 1.0 / W;
+#pragma unroll
+            for (int k = 0; k < MAXC; ++k)
+              if (k < C) p[kk][k] += (float)(v[k] * inv);
+          }
+        }
+      }
+    }
+    long long hitc[KC];
+#pragma unroll
+    for (int kk = 0; kk < KC; ++kk) {
+      int best = 0;
+      float bv = p[kk][0];
+#pragma unroll
+      for (int k = 1; k < MAXC; ++k)
+        if (k < C && p[kk][k] > bv) { bv = p[kk][k]; best = k; }
+      const bool on = live && k0 + kk < e.K;
+      hitc[kk] = on && best == label ? 1 : 0;
+      if (on && e.pred) ((int32_t*)e.pred)[((int64_t)blockIdx.y * e.K + k0 + kk) * nr + i] = best;
+    }
+    perm_block_sums<long long, KC>(e, hitc, red, k0);
+  }
+  perm_count_walked(e, nw);
+}
+
+template <int kPredU>
+__global__ __launch_bounds__(256) void k_perm_reg(PredictArgs a, PermTail e) {
+  constexpr int KC = 8;
+  extern __shared__ __attribute__((aligned(16))) uint8_t xs_lds[];
+  __shared__ double red[4][KC];
+  const int32_t* toff = GPTR(const int32_t, a.fit_tree_off);
+  const int64_t* roff = GPTR(const int64_t, a.fit_row_off);
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t r0 = roff[0], nr = roff[1] - r0;
+  if ((int64_t)blockIdx.x * 256 >= nr) return;
+  const bool live = i < nr;   // as in k_perm_cls: every thread stays
+  NodeRec* top = a.toptab ? (NodeRec*)(xs_lds + top_lds_off(a)) : nullptr;
+  const uint8_t* xr = a.lds_pitch ? stage_rows(a, xs_lds, r0, nr) : nullptr;
+  const int32_t row = (GPTR(const int32_t, a.rows))[r0 + (live ? i : 0)];
+  if (!a.lds_pitch) xr = GPTR(const uint8_t, a.Xb) + (int64_t)row * a.ld;
+  const int f = e.features[blockIdx.y];
+  const int own = f >= 0 ? xr[f] : 0;
+  const double y = ((const float*)e.y)[row];
+  const NodeRec* nodes = GPTR(const NodeRec, a.nodes);
+  const double* val = GPTR(const double, a.node_val);
+  const int tend = toff[1];
+  int nw = 0;
+  for (int k0 = 0; k0 < e.K; k0 += KC) {
+    int sub[KC];
+    perm_subs<KC>(a, e, i, nr, f, own, live, k0, sub);
+    double acc[KC];
+    int nt[KC];
+#pragma unroll
+    for (int kk = 0; kk < KC; ++kk) { acc[kk] = 0.0; nt[kk] = 0; }
+    for (int t = toff[0]; t < tend; t += kPredU) {
+      int base[kPredU];
+      const int u_all = min(kPredU, tend - t), u_n = live ? u_all : 0;
+      if (top) load_top<kPredU>(a, top, t, u_all);
+      uint32_t hit = 0;
+      leaves_perm_u<kPredU, true>(nodes, xr, t, u_n, base, e.cap, top, ~0u, f, 0, hit);
+      if (e.no_skip) hit = (1u << u_n) - 1u;
+      // the baseline leaves' means, computed once per group (as k_perm_cls keeps its fractions)
+      double bq[kPredU];
+      uint32_t bok = 0;
+#pragma unroll
+      for (int u = 0; u < kPredU; ++u) {
+        if (u >= u_n) continue;
+        const double* v = val + (int64_t)base[u] * a.VC;
+        if (v[0] > 0.0) { bq[u] = v[1] / v[0]; bok |= 1u << u; }
+      }
+#pragma unroll
+      for (int kk = 0; kk < KC; ++kk) {
+        if (k0 + kk >= e.K) break;
+        int lk[kPredU];
+        const uint32_t m = (sub[kk] != own || e.no_skip) ? hit : 0u;
+        if (m) {
+          uint32_t none = 0;
+          leaves_perm_u<kPredU, false>(nodes, xr, t, u_n, lk, e.cap, top, m, f, sub[kk], none);
+          nw += __popc(m);
+        }
+#pragma unroll
+        for (int u = 0; u < kPredU; ++u) {
+          if (u >= u_n) continue;
+          if (!((m >> u) & 1u)) {
+            if ((bok >> u) & 1u) { acc[kk] += bq[u]; ++nt[kk]; }
+            continue;
+          }
+          const double* v = val + (int64_t)(((m >> u) & 1u) ? lk[u] : base[u]) * a.VC;
+          if (v[0] > 0.0) { acc[kk] += v[1] / v[0]; ++nt[kk]; }
+        }
+      }
+    }
+    double se[KC];
+#pragma unroll
+    for (int kk = 0; kk < KC; ++kk) {
+      const float pr = nt[kk] ? (float)(acc[kk] / nt[kk]) : 0.f;
+      const bool on = live && k0 + kk < e.K;
+      const double er = (double)pr - y;
+      se[kk] = on ? er * er : 0.0;
+      if (on && e.pred) ((float*)e.pred)[((int64_t)blockIdx.y * e.K + k0 + kk) * nr + i] = pr;
+    }
+    perm_block_sums<double, KC>(e, se, red, k0);
+  }
+  perm_count_walked(e, nw);
+}
+
+// out[f][k] = the block partials added in block order (one thread per (f, k): the same sum every run)
+template <class T>
+__global__ __launch_bounds__(256) void k_perm_reduce(const T* __restrict__ part, T* __restrict__ out, int64_t blocks,
+                                                     int64_t FK) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j >= FK) return;
+  T s = 0;
+  for (int64_t b = 0; b < blocks; ++b) s += part[b * FK + j];
+  out[j] = s;
+}
+
 // per-fit score statistics: out[f] = {match_count or SSE, sum y, sum y^2, n}
 struct ScoreArgs {
   int64_t rows;        // int32[] row ids
@@ -616,6 +950,58 @@ static int launch_oob(const OobArgs* o, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
+// launch_oob's LDS layout with grid.y = feature; the kernels' own static LDS (stage_rows' row
+// list and the block sums) counts against the 64 KiB the dynamic part may fill
+template <int U>
+static int launch_perm(const PermArgs* o, hipStream_t st) {
+  PredictArgs a{};
+  a.Xb = o->Xb; a.ld = o->ld; a.d = o->d;
+  a.nodes = o->nodes; a.node_val = o->node_val; a.VC = o->VC; a.is_reg = o->is_reg; a.n_classes = o->n_classes;
+  a.fit_tree_off = o->fit_tree_off; a.fit_row_off = o->fit_row_off; a.rows = o->rows;
+  a.F = 1; a.max_rows = o->n_rows; a.max_trees = o->t1 - o->t0;
+  a.toptab = o->toptab;
+  constexpr size_t kStatic = 256 * sizeof(int32_t) + 4 * 8 * sizeof(double);
+  a.lds_pitch = predict_pitch(&a);
+  if ((size_t)a.lds_pitch * 256 + kStatic > 64 * 1024) a.lds_pitch = 0;
+  size_t lds = (size_t)a.lds_pitch * 256;
+  static const bool top_off = getenv("DML_PRED_NO_TOP") != nullptr;
+  const size_t lds_top = ((lds + 15) & ~(size_t)15) + (size_t)U * kTopSlots * sizeof(NodeRec);
+  if (top_off || lds_top + kStatic > 64 * 1024) a.toptab = 0;
+  if (a.toptab) {
+    k_top_fill<<<dim3((unsigned)((a.max_trees + 3) / 4), 1), 256, 0, st>>>(a);
+    lds = lds_top;
+  }
+  static const bool no_skip = getenv("DML_PERM_NO_SKIP") != nullptr;
+  const PermTail e{GPTR(const int32_t, o->perm), GPTR(const int32_t, o->features),
+                   o->is_reg ? (const void*)GPTR(const float, o->yreg) : (const void*)GPTR(const int32_t, o->ycls),
+                   GPTR(uint8_t, o->part), o->out_pred ? GPTR(uint8_t, o->out_pred) : nullptr,
+                   o->out_walked ? GPTR(unsigned long long, o->out_walked) : nullptr,
+                   (int)o->K, (int)o->F, o->depth_cap > 0 ? (int)o->depth_cap : 1 << 20,
+                   (no_skip || o->no_skip) ? 1 : 0};
+  const int64_t blocks = (o->n_rows + 255) / 256, FK = o->F * o->K;
+  const dim3 grid((unsigned)blocks, (unsigned)o->F);
+  const unsigned rgrid = (unsigned)((FK + 255) / 256);
+  if (o->is_reg) {
+    k_perm_reg<U><<<grid, 256, lds, st>>>(a, e);
+    k_perm_reduce<double><<<rgrid, 256, 0, st>>>(GPTR(const double, o->part), GPTR(double, o->out), blocks, FK);
+  } else {
+    const int C = (int)o->n_classes;
+    if (C <= 2) k_perm_cls<2, U><<<grid, 256, lds, st>>>(a, e);
+    else if (C <= 4) k_perm_cls<4, U><<<grid, 256, lds, st>>>(a, e);
+    else if (C <= 8) k_perm_cls<8, U><<<grid, 256, lds, st>>>(a, e);
+    else if (C <= 16) k_perm_cls<16, U><<<grid, 256, lds, st>>>(a, e);
+    else if (C <= 32) k_perm_cls<32, U><<<grid, 256, lds, st>>>(a, e);
+    else if (C <= 64) {
+      // 64 class sums with 16 lock-step walks: the slot loops are too large to unroll and the leaf
+      // arrays would live in scratch -- dml_forest_perm sends these through the 8-wide walk
+      if constexpr (U < 16) k_perm_cls<64, U><<<grid, 256, lds, st>>>(a, e);
+      else return 5;
+    } else return 5;
+    k_perm_reduce<long long><<<rgrid, 256, 0, st>>>(GPTR(const long long, o->part), GPTR(long long, o->out), blocks, FK);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
 // max_leaf_nodes: one lane per limited tree replays sklearn's best-first order over the
 // grown tree (forest_common.h best_first_prune); the frontier heap lives in global
 // scratch, ``cap`` entries per lane.  Trees with limit 0 are left alone.
@@ -703,6 +1089,19 @@ int dml_forest_oob(const OobArgs* o, hipStream_t st) {
   if (u == 16) return launch_oob<16>(o, st);
   if (u == 4) return launch_oob<4>(o, st);
   return launch_oob<8>(o, st);
+}
+
+int dml_perm_sizeof_args() { return (int)sizeof(PermArgs); }
+
+// permutation-importance score statistics of one kept fit over its held-out rows
+// (k_perm_cls / k_perm_reg, then k_perm_reduce)
+int dml_forest_perm(const PermArgs* o, hipStream_t st) {
+  if (o->n_rows <= 0 || o->F <= 0 || o->K <= 0) return 0;
+  if (o->t1 <= o->t0 || o->t0 < 0 || o->F > 65535 || !o->part || !o->out) return 2;
+  static const int u = [] { const char* e = getenv("DML_PRED_U"); return e ? atoi(e) : 8; }();
+  if (u == 16 && (o->is_reg || o->n_classes <= 32)) return launch_perm<16>(o, st);
+  if (u == 4) return launch_perm<4>(o, st);
+  return launch_perm<8>(o, st);
 }
 
 int dml_scores(ScoreArgs* a, hipStream_t st) {

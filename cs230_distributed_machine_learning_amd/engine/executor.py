@@ -48,6 +48,10 @@ class JobSpec:
     keep_models: str = "best"                 # none | best | all
     seed: int = 0
     raise_batch_errors: bool = False          # device errors propagate (the caller retries the batch)
+    # train_params["permutation_importance"] as service.job_plan resolved it (RandomForest* only):
+    # with candidates == "all" every candidate's holdout fit computes it; "best" is one extra fit
+    # after aggregation (holdout_permutation)
+    permutation: Optional[Dict[str, Any]] = None
 
     def split_key(self):
         return (self.cv, self.holdout, str(self.test_size), str(self.random_state), is_classifier(self.model_type))
@@ -169,11 +173,14 @@ def run_candidates(data, spec: JobSpec, candidate_ids: Sequence[int]) -> List[Ca
         from ..ops import forest_ops
 
         forest_ops.ARENA.clear(data.device)   # idle forest buffers back to the device for this family
-    keep = spec.keep_models in ("all", "best")
+    perm_all = bool(spec.permutation) and spec.permutation.get("candidates") == "all" and "holdout" in names
+    keep = spec.keep_models in ("all", "best") or perm_all   # the importances ride on the holdout fit's model
     if keep and "holdout" in names:   # only the holdout fit's model is reported (J4 model_path)
         hold = names.index("holdout")
         for t in tasks:
             t.keep = t.split == hold
+            if perm_all and t.keep:
+                t.permutation = spec.permutation
     outputs: Dict[int, FitOutput] = {}
     if tasks:
         try:
@@ -252,6 +259,16 @@ def run_candidates(data, spec: JobSpec, candidate_ids: Sequence[int]) -> List[Ca
                     for w in o.info.get("warnings", []):   # the kept fit's own (rows no tree left out)
                         if w not in warnings:
                             warnings.append(w)
+                entry = permutation_entry(model)
+                if entry is not None:
+                    R["permutation_importance"] = entry
+                if spec.permutation:
+                    from ..models.forest import PERM_SHARDED
+
+                    if sharded and PERM_SHARDED not in warnings:
+                        warnings.append(PERM_SHARDED)
+                    if spec.keep_models not in ("all", "best"):   # kept for the importances only
+                        model = None
             else:
                 R["training_time"] = fit_s
             if cv_idx:
@@ -277,6 +294,40 @@ def run_candidates(data, spec: JobSpec, candidate_ids: Sequence[int]) -> List[Ca
             R["parameters"] = spec.candidates[c]
             results.append(CandidateResult(candidate=c, ok=True, result=R, model=model, fit_seconds=fit_s))
     return results
+
+
+PERM_MODEL_KEYS = ("permutation_importances_mean", "permutation_importances_std", "permutation_baseline_score",
+                   "permutation_rows", "permutation_meta")
+
+
+def permutation_entry(model) -> Optional[Dict[str, Any]]:
+    """The ``permutation_importance`` entry of a J4 result from a model that carries the arrays."""
+    if not isinstance(model, dict) or model.get("permutation_importances_mean") is None:
+        return None
+    meta = model.get("permutation_meta") or {}
+    return {"importances_mean": [float(v) for v in model["permutation_importances_mean"]],
+            "importances_std": [float(v) for v in model["permutation_importances_std"]],
+            "baseline_score": float(model["permutation_baseline_score"]),
+            "scoring": meta.get("scoring"), "n_repeats": meta.get("n_repeats"),
+            "random_state": meta.get("random_state")}
+
+
+def holdout_permutation(data, spec: JobSpec, candidate: int) -> Optional[Dict[str, Any]]:
+    """``candidates == "best"``: fit one candidate once more on the job's holdout split, with the
+    seed its first holdout fit had (the same trees, so the baseline is the holdout score already
+    in its result), and return that fit's model with the permutation arrays.  None under a row
+    shard, where nothing is computed."""
+    if getattr(data, "is_row_shard", False):
+        return None
+    names = prepare_splits(data, spec)
+    tasks, errors = build_tasks(data, spec, [candidate])
+    if errors or "holdout" not in names:
+        return None
+    hold = names.index("holdout")
+    task = [t for t in tasks if t.split == hold][0]
+    task.keep, task.permutation = True, spec.permutation
+    out = family_of(spec.model_type).run(data, [task], keep_models=True)[0]
+    return None if out.error else out.model
 
 
 def _failed(c: int, spec: JobSpec, err: str) -> CandidateResult:

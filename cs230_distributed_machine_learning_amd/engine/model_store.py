@@ -22,13 +22,15 @@ from __future__ import annotations
 import json
 import os
 import re
+from dataclasses import dataclass
 from typing import Any, Dict, Optional
 
 import numpy as np
 
 _ARRAY_KEYS = ("nodes", "vals", "edges", "coef", "intercept", "X", "y", "init", "stage_offsets", "scale", "mean",
                "components", "var", "min", "max", "value", "roots", "feature_importances", "oob_rows",
-               "oob_decision_function", "oob_prediction")
+               "oob_decision_function", "oob_prediction", "permutation_importances", "permutation_importances_mean",
+               "permutation_importances_std", "permutation_baseline_score", "permutation_rows")
 
 
 def save_model(model: Dict[str, Any], path: str) -> str:
@@ -141,6 +143,21 @@ def _softmax(z: np.ndarray) -> np.ndarray:
 
 
 _REGRESSOR_KINDS = ("linear_regression",)
+
+
+@dataclass
+class PermutationImportance:
+    """``Predictor.permutation_importance_``: sklearn's Bunch fields, plus what they were computed
+    on.  ``importances`` [d, K] is in the holdout fit's artefact only (None in a refit one)."""
+
+    importances_mean: np.ndarray
+    importances_std: np.ndarray
+    baseline_score: float
+    rows: np.ndarray                 # dataset row ids that were scored (the fit's held-out rows)
+    importances: Optional[np.ndarray] = None
+    scoring: Optional[str] = None
+    n_repeats: Optional[int] = None
+    random_state: Optional[int] = None
 
 
 class Predictor:
@@ -309,6 +326,24 @@ class Predictor:
     def oob_rows_(self) -> np.ndarray:
         """Dataset row ids the out-of-bag arrays are aligned with (the fit's training rows)."""
         return np.asarray(self._oob("oob_rows", "oob_rows_"))
+
+    @property
+    def permutation_importance_(self) -> "PermutationImportance":
+        """sklearn's ``permutation_importance`` result on the fit's held-out rows
+        (docs/PERMUTATION_IMPORTANCE.md); a refit artefact carries its holdout fit's values."""
+        m = self.model if self.kind == "forest" else {}
+        if m.get("permutation_importances_mean") is None:
+            raise AttributeError(f"{self.model_type} artefact has no permutation_importance_ (train with "
+                                 f"train_params[\"permutation_importance\"])")
+        meta = m.get("permutation_meta") or {}
+        imp = m.get("permutation_importances")
+        return PermutationImportance(
+            importances_mean=np.asarray(m["permutation_importances_mean"], dtype=np.float64),
+            importances_std=np.asarray(m["permutation_importances_std"], dtype=np.float64),
+            baseline_score=float(m["permutation_baseline_score"]),
+            rows=np.asarray(m["permutation_rows"]),
+            importances=None if imp is None else np.asarray(imp, dtype=np.float64),
+            scoring=meta.get("scoring"), n_repeats=meta.get("n_repeats"), random_state=meta.get("random_state"))
 
     # ---- transformers ------------------------------------------------------------------
     def transform(self, X) -> np.ndarray:

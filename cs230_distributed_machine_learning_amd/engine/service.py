@@ -56,6 +56,55 @@ def _cv_from(cv_params: Dict[str, Any]) -> int:
     raise ParamError(f"unsupported cv specification {cv!r} (use an int)")
 
 
+PERM_KEYS = ("n_repeats", "random_state", "scoring", "candidates")
+
+
+def permutation_options(tp: Dict[str, Any], model_type: str, holdout: bool, job_id) -> Optional[Dict[str, Any]]:
+    """``train_params["permutation_importance"]`` (True or a dict of ``PERM_KEYS``) resolved to
+    {"n_repeats", "random_state", "scoring", "candidates"}; None when the job does not ask.
+    ``random_state=None`` draws the seed once per job (from its id, so every worker and a resumed
+    job use the same one); the result reports the seed used."""
+    import zlib
+
+    from ..ops.forest_ops import PERM_SCORERS
+
+    v = tp.get("permutation_importance")
+    if v is None or v is False:
+        return None
+    if v is True:
+        v = {}
+    if not isinstance(v, dict):
+        raise ParamError("train_params.permutation_importance must be true or a dict of "
+                         f"{', '.join(PERM_KEYS)}")
+    unknown = sorted(k for k in v if k not in PERM_KEYS)
+    if unknown:
+        raise ParamError(f"permutation_importance: unknown key(s) {unknown}; supported: {list(PERM_KEYS)}")
+    if model_type not in ("RandomForestClassifier", "RandomForestRegressor"):
+        raise ParamError(f"permutation_importance is available for RandomForestClassifier and "
+                         f"RandomForestRegressor, not {model_type}")
+    if not holdout:
+        raise ParamError("permutation_importance needs holdout=True: it scores the held-out rows")
+    k = v.get("n_repeats", 5)
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ParamError(f"permutation_importance: n_repeats must be an int >= 1, got {k!r}")
+    is_reg = model_type == "RandomForestRegressor"
+    scoring = v.get("scoring")
+    if scoring in (None, "None", ""):
+        scoring = PERM_SCORERS[is_reg][0]
+    if scoring not in PERM_SCORERS[is_reg]:
+        raise ParamError(f"permutation_importance: scoring {scoring!r} is not supported for {model_type}; "
+                         f"supported: {list(PERM_SCORERS[is_reg])}")
+    cands = v.get("candidates", "best")
+    if cands not in ("best", "all"):
+        raise ParamError(f"permutation_importance: candidates must be 'best' or 'all', got {cands!r}")
+    rs = v.get("random_state", 0)
+    if rs is None:
+        rs = zlib.crc32(f"{job_id}:permutation".encode()) & 0x7FFFFFFF
+    if isinstance(rs, bool) or not isinstance(rs, int) or not 0 <= rs < 2**32:
+        raise ParamError(f"permutation_importance: random_state must be None or an int in [0, 2**32), got {rs!r}")
+    return {"n_repeats": int(k), "random_state": int(rs), "scoring": scoring, "candidates": cands}
+
+
 def job_plan(request: Dict[str, Any]) -> Dict[str, Any]:
     """Derive everything a worker needs from a J1 request."""
     md = request.get("model_details") or {}
@@ -88,7 +137,8 @@ def job_plan(request: Dict[str, Any]) -> Dict[str, Any]:
         raise ParamError(f"train_params.parallelism must be 'auto', 'task' or 'data', got {par!r}")
     if par == "data" and not getattr(family_of(model_type), "data_parallel", False):
         raise ParamError(f"{model_type} has no row-sharded (data-parallel) fit; use parallelism 'task'")
-    return {
+    perm = permutation_options(tp, model_type, bool(tp.get("holdout", True)), request.get("job_id"))
+    plan = {
         "model_type": model_type, "search_type": search_type, "candidates": cands, "cv": cv,
         "scoring": scoring, "error_score": error_score, "refit": bool(refit) if not isinstance(refit, str) else True,
         "test_size": tp.get("test_size", 0.2) if tp.get("test_size") is not None else 0.2,   # D2
@@ -100,6 +150,9 @@ def job_plan(request: Dict[str, Any]) -> Dict[str, Any]:
         # planner reads random_state from them (prefix_units)
         "base_params": dict(hp.get("base_estimator_params") or {}) if search_type else dict(hp),
     }
+    if perm is not None:   # a job that does not ask carries no such key
+        plan["permutation_importance"] = perm
+    return plan
 
 
 def scheduler_state_path(config: Config) -> Optional[str]:
@@ -497,7 +550,7 @@ def run_slice(plan: Dict[str, Any], params: List[Dict[str, Any]], subtask_ids: L
     spec = JobSpec(model_type=plan["model_type"], candidates=params, cv=plan["cv"], scoring=plan["scoring"],
                    holdout=plan["holdout"], test_size=plan["test_size"], random_state=plan["random_state"],
                    error_score=plan["error_score"], keep_models="all" if keep_all else "none", seed=seed,
-                   raise_batch_errors=True)
+                   raise_batch_errors=True, permutation=plan.get("permutation_importance"))
     received = utc_iso()
     slice_key = ",".join(str(int(c)) for c in cand_ids)
     gpu = dd.device.index if dd.is_gpu else None
@@ -677,11 +730,59 @@ def refit_model(plan: Dict[str, Any], params: Dict[str, Any], dd) -> Optional[Di
     return outs[0].model
 
 
-def refit_best(ctl: Controller, job: Job, plan: Dict[str, Any], dd, best_idx: int) -> Optional[str]:
-    """sklearn refit=True: fit the best candidate on all rows and store the artefact."""
-    from .executor import JobSpec, run_candidates
+def best_permutation(plan: Dict[str, Any], params: List[Dict[str, Any]], dd, best_idx: int,
+                     seed: int) -> Optional[Dict[str, Any]]:
+    """``permutation_importance`` of the job's best candidate: one more fit on the job's holdout
+    split with the candidate's own seed, and the fused walk over its held-out rows
+    (executor.holdout_permutation).  Called before the refit re-labels the splits.  Returns the
+    holdout fit's model (the arrays under ``executor.PERM_MODEL_KEYS``), or None."""
+    from .executor import JobSpec, holdout_permutation
 
-    model = refit_model(plan, job.subtasks[best_idx].spec["parameters"], dd)
+    spec = JobSpec(model_type=plan["model_type"], candidates=params, cv=plan["cv"], scoring=plan["scoring"],
+                   holdout=plan["holdout"], test_size=plan["test_size"], random_state=plan["random_state"],
+                   error_score=plan["error_score"], keep_models="all", seed=seed,
+                   permutation=plan["permutation_importance"])
+    return holdout_permutation(dd, spec, best_idx)
+
+
+def refit_with_permutation(plan: Dict[str, Any], params: List[Dict[str, Any]], dd, best_idx: int, seed: int):
+    """(the refit model or None, the winner's ``permutation_importance`` result entry or None).
+    The holdout fit comes first: the refit re-labels the resident splits.  Controller-free, so
+    the cluster runner's refit on rank 0 runs exactly this."""
+    from .executor import PERM_MODEL_KEYS, permutation_entry
+
+    perm_model = None
+    if plan.get("permutation_importance"):
+        try:
+            perm_model = best_permutation(plan, params, dd, best_idx, seed)
+        except Exception:   # the job still gets its refit model
+            traceback.print_exc()
+    entry = permutation_entry(perm_model)
+    model = refit_model(plan, params[best_idx], dd)
+    if model is not None and entry is not None:
+        for k in PERM_MODEL_KEYS:
+            model[k] = perm_model[k]
+    return model, entry
+
+
+def attach_permutation(ctl: Controller, job: Job, results, cand: int, entry: Dict[str, Any]) -> None:
+    """The winner's importances go on its J4 result like the refit model's path (``attach_model``)."""
+    for r in results:
+        if r.candidate == cand and r.ok:
+            r.result["permutation_importance"] = entry
+            return
+    ctl.table.update_result(job.job_id, job.subtasks[cand].subtask_id, {"permutation_importance": json_safe(entry)})
+
+
+def refit_best(ctl: Controller, job: Job, plan: Dict[str, Any], dd, best_idx: int, results=None) -> Optional[str]:
+    """sklearn refit=True: fit the best candidate on all rows and store the artefact.  A job with
+    ``permutation_importance`` first fits the winner once more on the holdout split: its
+    importances go on the winner's result (in ``results`` when it is there, else on its published
+    subtask) and, unchanged, into the refit artefact, which has no held-out rows of its own."""
+    model, entry = refit_with_permutation(plan, [st.spec["parameters"] for st in job.subtasks], dd, best_idx,
+                                          job_seed(job.job_id))
+    if entry is not None:
+        attach_permutation(ctl, job, results or [], best_idx, entry)
     if model is None:
         return None
     model["job_id"] = job.job_id
@@ -841,7 +942,7 @@ def finalize_job(ctl: Controller, job: Job, plan: Dict[str, Any], dd, results) -
     if best is None:
         return
     try:
-        path = refit_best(ctl, job, plan, dd, best)
+        path = refit_best(ctl, job, plan, dd, best, results)
         if path:
             attach_model(ctl, job, results, best, path)
     except Exception:

@@ -29,6 +29,9 @@ class FitTask:
     keep: bool = True           # with keep_models: this fit's model is wanted (holdout fits only, when there is one)
     need_proba: bool = False    # the job's scorer reads class probabilities (roc_auc, neg_log_loss, ...)
     scorer: Optional[str] = None   # that scorer's name (SVC: some of them read the decision values instead)
+    # RandomForest*: {"n_repeats", "random_state", "scoring"} -- a kept fit also computes sklearn's
+    # permutation importance on its held-out rows (models/forest.py _attach_perm)
+    permutation: Optional[Dict[str, Any]] = None
 
 
 @dataclass

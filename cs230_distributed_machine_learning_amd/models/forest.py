@@ -17,7 +17,10 @@ ops/forest_ops.py oob_predict over the fit's training rows gives oob_score,
 oob_decision_function / oob_prediction and oob_rows; CV fits do no extra work; not computed
 for row-sharded jobs).  Every kept model also carries sklearn's feature_importances (mean
 decrease in impurity from the pool's node sums, forest_ops.feature_importances; not for
-criterion poisson / absolute_error, whose impurities the pool does not hold).  Parameters
+criterion poisson / absolute_error, whose impurities the pool does not hold).  A kept fit whose
+task carries ``FitTask.permutation`` (the job's train_params["permutation_importance"]) also gets
+sklearn's permutation importance on its held-out rows (_attach_perm,
+docs/PERMUTATION_IMPORTANCE.md).  Parameters
 with no effect on the fitted function (n_jobs, verbose, warm_start) are
 accepted and ignored; class_weight (dict / "balanced" / "balanced_subsample") scales
 the per-class sums inside the builder exactly where sklearn's sample weights would;
@@ -41,12 +44,14 @@ import numpy as np
 import torch
 
 from ..ops import forest_ops
+from ..search import scoring as scoring_mod
 from ..utils import native, trace
 from .base import (Family, FitOutput, FitTask, ParamError, as_bool, as_float, as_int, prefix_groups, register,
                    seed_of)
 
 _CLS = "RandomForestClassifier"
 _REG = "RandomForestRegressor"
+PERM_SHARDED = "permutation_importance is not computed for row-sharded jobs (run with parallelism='task')"
 
 _DEFAULT = object()   # "parameter not given"
 
@@ -299,6 +304,8 @@ class ForestFamily(Family):
                 msg = "oob_score is not computed for row-sharded jobs (run with parallelism='task')"
                 if t.params.get("oob_score") and msg not in t.params["warnings"]:
                     t.params["warnings"] = t.params["warnings"] + [msg]
+                if t.permutation and PERM_SHARDED not in t.params["warnings"]:
+                    t.params["warnings"] = t.params["warnings"] + [PERM_SHARDED]
         # absolute_error trees grow on their own builder (forest_mae.hip / forest_cpu.cpp): batch them apart
         tasks_in = tasks
         # fits differing only in n_estimators with an explicit random_state grow the same first
@@ -543,6 +550,7 @@ class ForestFamily(Family):
                 if keep_models and t.keep:
                     o.model = extract_forest(fb, int(toff[f]), int(toff[f + 1]), data, t)
                     self._attach_oob(data, Xb, fb, specs, o, int(toff[f]), int(toff[f + 1]), t, 0)
+                    self._attach_perm(data, Xb, fb, o, int(toff[f]), int(toff[f + 1]), t, 0)
                 outs.append(o)
                 for fo in (follow or {}).get(t.task_id, []):   # prefix fits: leader f's first m trees
                     m = int(fo.params["n_estimators"])
@@ -564,6 +572,7 @@ class ForestFamily(Family):
                     if keep_models and fo.keep:
                         of.model = extract_forest(fb, int(toff[f]), int(toff[f]) + m, data, fo, depth_cap=cap)
                         self._attach_oob(data, Xb, fb, specs, of, int(toff[f]), int(toff[f]) + m, fo, cap)
+                        self._attach_perm(data, Xb, fb, of, int(toff[f]), int(toff[f]) + m, fo, cap)
                     outs.append(of)
             return outs
         finally:   # the node pool is an arena slot: free it for the next batch
@@ -591,6 +600,32 @@ class ForestFamily(Family):
         out.model["oob_score"] = float(score)
         out.model["oob_rows"] = to_np(rows).astype(np.int32)
         out.model["oob_prediction" if is_reg else "oob_decision_function"] = to_np(dec).astype(np.float32)
+
+    def _attach_perm(self, data, Xb, fb, out: FitOutput, t0: int, t1: int, task: FitTask, cap: int) -> None:
+        """``FitTask.permutation`` on a kept fit: sklearn's permutation importance of pool trees
+        [t0, t1) on the fit's held-out rows (forest_ops.permutation_scores: one fused walk for
+        every feature and repeat), attached to the model ``extract_forest`` returned.  A fit
+        without the option launches and allocates nothing."""
+        opts = task.permutation
+        rows = data.test_rows[task.split]
+        if not opts or getattr(data, "is_row_shard", False) or int(rows.numel()) == 0:   # run() warned a sharded job
+            return
+        on = fb.on_gpu
+        perm = forest_ops.permutation_indices(int(rows.numel()), opts["n_repeats"], opts["random_state"])
+        sc = forest_ops.permutation_scores(fb, Xb if on else Xb.numpy(), t0, t1, rows if on else rows.numpy(), perm,
+                                           ycls=data.y_cls, yreg=data.y_reg, depth_cap=cap)
+        pi = forest_ops.permutation_importance(sc, opts["scoring"])
+        # the reported baseline is the job's own scorer on the fit's own predictions of these rows
+        # (the walk's unpermuted sums give the same score up to the order of an SSE sum)
+        base = scoring_mod.score(pi["scoring"], data.test_targets(task.split), out.pred, data.n_classes)
+        m = out.model
+        m["permutation_importances"] = pi["importances"]
+        m["permutation_importances_mean"] = pi["importances_mean"]
+        m["permutation_importances_std"] = pi["importances_std"]
+        m["permutation_baseline_score"] = np.float64(base)
+        m["permutation_rows"] = (rows.cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)).astype(np.int32)
+        m["permutation_meta"] = {"scoring": pi["scoring"], "n_repeats": int(opts["n_repeats"]),
+                                 "random_state": int(opts["random_state"])}
 
 
 def _early_ok(data, batch: List[FitTask], is_reg: bool, mono) -> bool:

@@ -949,6 +949,176 @@ def oob_score(rows, pred, ycls=None, yreg=None, is_reg: bool = False) -> float:
     return 1.0 - float(s[0]) / ss_tot
 
 
+PERM_SCORERS = {False: ("accuracy",), True: ("r2", "neg_mean_squared_error", "neg_root_mean_squared_error")}
+
+
+def permutation_indices(n: int, n_repeats: int, random_state) -> np.ndarray:
+    """The index stream of ``sklearn.inspection.permutation_importance(random_state=...)`` with
+    ``max_samples=1.0``: int32 [K, n], ``perm[k][i]`` the position whose value row i gets in repeat
+    k.  sklearn draws one seed and gives every feature a RandomState of that seed, so one stream
+    serves all features; it shuffles the already permuted column again for each repeat, hence the
+    cumulative ``e = e[s]`` (``s`` itself is shuffled in place from its previous state)."""
+    rs = np.random.RandomState(random_state)
+    r = np.random.RandomState(rs.randint(np.iinfo(np.int32).max + 1))
+    s, e = np.arange(n), np.arange(n)
+    perm = np.empty((int(n_repeats), n), dtype=np.int32)
+    for k in range(int(n_repeats)):
+        r.shuffle(s)
+        e = e[s]
+        perm[k] = e
+    return perm
+
+
+def used_features(fb: ForestBuild, t0: int, t1: int, d: int, depth_cap: int = 0) -> np.ndarray:
+    """Ascending ids of the features some node of pool trees [t0, t1) splits on (nodes below
+    ``depth_cap`` levels, when given, are not read by the walk and do not count)."""
+    nodes = fb.nodes if isinstance(fb.nodes, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(fb.nodes))
+    seen = torch.zeros(d, dtype=torch.bool, device=nodes.device)
+    fo = torch.arange(t0, t1, dtype=torch.int64, device=nodes.device)
+    level = 0
+    while fo.numel() and (depth_cap <= 0 or level < depth_cap):
+        rec = nodes[fo]
+        internal = rec[:, 0] >= 0
+        seen[(rec[internal, 0].to(torch.int64) >> 8).clamp_(0, d - 1)] = True
+        l = rec[internal, 1].to(torch.int64)
+        fo = torch.stack([l, l + 1], 1).reshape(-1)
+        level += 1
+    return torch.nonzero(seen).reshape(-1).cpu().numpy().astype(np.int32)
+
+
+def permutation_scores(fb: ForestBuild, Xb, t0: int, t1: int, rows, perm, ycls=None, yreg=None, depth_cap: int = 0,
+                       want_pred: bool = False, want_walked: bool = False, no_skip: bool = False) -> dict:
+    """Score statistics of pool trees [t0, t1) over ``rows`` (ascending dataset row ids) with one
+    feature at a time taken from another row: for feature f and repeat k, row i is predicted
+    from its own bins except that f's bin is that of row ``rows[perm[k][i]]`` (``perm`` int32
+    [K, n], ``permutation_indices``).  The prediction rule is ``predict``'s, bit for bit.  GPU
+    pool: predict.hip ``k_perm_cls`` / ``k_perm_reg``; host pool: the twin,
+    csrc/runtime/forest_perm_cpu.cpp.  A feature no node of the trees splits on is not walked:
+    its statistics are the baseline's.  Returns, on the pool's device,
+
+    * ``base``: float64 [4] = (match count | SSE, sum y, sum y^2, n) of the unpermuted rows, with
+      ``ss_tot`` = sum (y - mean y)^2 beside it for regression;
+    * ``sums``: [d, K], int64 match counts (classification) or float64 SSE (regression);
+    * ``features``: the walked feature ids; with ``want_pred`` also ``pred`` [d, K, n] (int32 class
+      / float32) and ``base_pred`` [n]; with ``want_walked`` the number of (row, tree, repeat)
+      slots per feature [d] that were walked a second time."""
+    is_reg, C = bool(fb.is_reg), int(fb.n_classes)
+    d = int(Xb.shape[1])
+    if not 0 <= t0 < t1 <= int(fb.n_trees):
+        raise ValueError(f"permutation_scores: trees [{t0}, {t1}) outside the pool's {fb.n_trees} trees")
+    perm_np = np.ascontiguousarray(perm.cpu().numpy() if isinstance(perm, torch.Tensor) else perm, dtype=np.int32)
+    rows_np = np.ascontiguousarray(rows.cpu().numpy() if isinstance(rows, torch.Tensor) else rows, dtype=np.int32)
+    n = len(rows_np)
+    if perm_np.ndim != 2 or perm_np.shape[1] != n or perm_np.shape[0] < 1:
+        raise ValueError("permutation_scores: perm must be [K >= 1, len(rows)]")
+    K = int(perm_np.shape[0])
+    if n == 0:
+        raise ValueError("permutation_scores: no rows")
+    if perm_np.min() < 0 or perm_np.max() >= n or rows_np.min() < 0 or rows_np.max() >= int(Xb.shape[0]):
+        raise ValueError("permutation_scores: an index is out of range")
+    y = yreg if is_reg else ycls
+    if y is None or int(y.shape[0]) < int(Xb.shape[0]):
+        raise ValueError("permutation_scores: the target must cover every dataset row")
+    used = used_features(fb, t0, t1, d, depth_cap)
+    feats = np.concatenate([np.array([-1], dtype=np.int32), used])   # slot 0: the baseline
+    F = len(feats)
+    blocks = (n + 255) // 256
+    sdt_np, sdt_t = (np.float64, torch.float64) if is_reg else (np.int64, torch.int64)
+    pdt_np, pdt_t = (np.float32, torch.float32) if is_reg else (np.int32, torch.int32)
+    if fb.on_gpu:
+        dev = fb.nodes.device
+        rows_t = (rows if isinstance(rows, torch.Tensor) else torch.from_numpy(rows_np)).to(dev, torch.int32).contiguous()
+        perm_t, feats_t = torch.from_numpy(perm_np).to(dev), torch.from_numpy(feats).to(dev)
+        y_t = (y if isinstance(y, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(y))).to(dev)
+        y_t = y_t.to(torch.float32 if is_reg else torch.int32).contiguous()
+        toff = torch.tensor([t0, t1], dtype=torch.int32).to(dev)
+        roff = torch.tensor([0, n], dtype=torch.int64).to(dev)
+        part = torch.empty((blocks, F, K), dtype=sdt_t, device=dev)
+        out = torch.empty((F, K), dtype=sdt_t, device=dev)
+        pred = torch.empty((F, K, n), dtype=pdt_t, device=dev) if want_pred else None
+        walked = torch.zeros(F, dtype=torch.int64, device=dev) if want_walked else None
+        top = torch.empty((int(t1) * TOP_SLOTS_MAX, 2), dtype=torch.int32, device=dev)   # indexed by pool tree id
+        o = native.PermArgs()
+        o.Xb, o.ld, o.d = native.ptr(Xb), Xb.stride(0), d
+        o.nodes, o.node_val, o.VC = native.ptr(fb.nodes), native.ptr(fb.vals), int(fb.VC)
+        o.is_reg, o.n_classes = int(is_reg), C
+        o.fit_tree_off, o.fit_row_off, o.t0, o.t1 = native.ptr(toff), native.ptr(roff), int(t0), int(t1)
+        o.rows, o.n_rows, o.depth_cap = native.ptr(rows_t), n, int(depth_cap)
+        o.perm, o.K, o.features, o.F = native.ptr(perm_t), K, native.ptr(feats_t), F
+        o.ycls, o.yreg = (0, native.ptr(y_t)) if is_reg else (native.ptr(y_t), 0)
+        o.part, o.out, o.out_pred, o.out_walked = native.ptr(part), native.ptr(out), native.ptr(pred), native.ptr(walked)
+        o.toptab, o.no_skip = native.ptr(top), int(no_skip)
+        with trace.range("forest_perm"):
+            rc = native.hip_lib().dml_forest_perm(ctypes.byref(o), native.stream_handle(dev))
+        if rc:
+            raise RuntimeError(f"dml_forest_perm failed ({rc})")
+        torch.cuda.current_stream(dev).synchronize()   # keep the scratch and index arrays alive until done
+        yv = y_t[rows_t.long()].double()
+        used_t = torch.from_numpy(used.astype(np.int64)).to(dev)
+    else:
+        dev = torch.device("cpu")
+        Xb_np = np.ascontiguousarray(Xb.numpy() if isinstance(Xb, torch.Tensor) else Xb)
+        y_np = np.ascontiguousarray(y.cpu().numpy() if isinstance(y, torch.Tensor) else y,
+                                    dtype=np.float32 if is_reg else np.int32)
+        nodes = np.ascontiguousarray(fb.nodes, dtype=np.int32)
+        vals = np.ascontiguousarray(fb.vals, dtype=np.float64)
+        part_np = np.empty((blocks, F, K), dtype=sdt_np)
+        out_np = np.empty((F, K), dtype=sdt_np)
+        pred_np = np.empty((F, K, n), dtype=pdt_np) if want_pred else None
+        walked_np = np.zeros(F, dtype=np.uint64) if want_walked else None
+        native.cpu_lib().dml_cpu_forest_perm(
+            native.ptr(Xb_np), Xb_np.shape[1], native.ptr(nodes), native.ptr(vals), int(fb.VC), int(is_reg), C,
+            int(t0), int(t1), native.ptr(rows_np), n, int(depth_cap), native.ptr(perm_np), K, native.ptr(feats), F,
+            0 if is_reg else native.ptr(y_np), native.ptr(y_np) if is_reg else 0, native.ptr(part_np),
+            native.ptr(out_np), native.ptr(pred_np), native.ptr(walked_np))
+        out = torch.from_numpy(out_np)
+        pred = torch.from_numpy(pred_np) if want_pred else None
+        walked = torch.from_numpy(walked_np.astype(np.int64)) if want_walked else None
+        yv = torch.from_numpy(y_np[rows_np]).double()
+        used_t = torch.from_numpy(used.astype(np.int64))
+    sums = out[0, :1].expand(d, K).clone()       # unwalked features: the baseline's statistic
+    sums[used_t] = out[1:]
+    base = torch.zeros(4, dtype=torch.float64, device=dev)
+    base[0], base[3] = out[0, 0].double(), float(n)
+    res = {"base": base, "sums": sums, "features": used, "n": n, "is_reg": is_reg}
+    if is_reg:
+        base[1], base[2] = yv.sum(), (yv * yv).sum()
+        res["ss_tot"] = float(((yv - yv.mean()) ** 2).sum())
+    if want_pred:
+        full = pred[0, :1].expand(d, K, n).clone()
+        full[used_t] = pred[1:]
+        res["pred"], res["base_pred"] = full, pred[0, 0].clone()
+    if want_walked:
+        res["walked"] = torch.zeros(d, dtype=torch.int64, device=dev).index_put_((used_t,), walked[1:])
+    return res
+
+
+def permutation_importance(scores: dict, scoring: Optional[str] = None) -> dict:
+    """``permutation_scores``' sums as sklearn's result: ``baseline_score``, ``importances`` [d, K]
+    = baseline_score - score[f, k], ``importances_mean`` and ``importances_std`` (``np.std``,
+    ddof 0), all float64 on the host.  Scorers: ``accuracy`` (classifiers); ``r2`` (default),
+    ``neg_mean_squared_error``, ``neg_root_mean_squared_error`` (regressors), with the formulas of
+    search/scoring.py (r2 against sum (y - mean y)^2; a constant target scores 1 or 0)."""
+    is_reg, n = bool(scores["is_reg"]), int(scores["n"])
+    name = scoring if scoring not in (None, "None", "") else PERM_SCORERS[is_reg][0]
+    if name not in PERM_SCORERS[is_reg]:
+        raise ValueError(f"permutation importance scoring must be one of {list(PERM_SCORERS[is_reg])}, got {name!r}")
+    stat = np.concatenate([scores["base"][:1].cpu().numpy().astype(np.float64),
+                           scores["sums"].cpu().numpy().astype(np.float64).reshape(-1)])
+    if name == "accuracy":
+        sc = stat / n
+    elif name == "r2":
+        tot = float(scores["ss_tot"])
+        sc = np.where(stat == 0.0, 1.0, 0.0) if tot == 0.0 else 1.0 - stat / tot
+    elif name == "neg_mean_squared_error":
+        sc = -(stat / n)
+    else:
+        sc = -np.sqrt(stat / n)
+    imp = (sc[0] - sc[1:]).reshape(scores["sums"].shape)
+    return {"baseline_score": float(sc[0]), "importances": imp, "importances_mean": imp.mean(1),
+            "importances_std": imp.std(1), "scoring": name}
+
+
 def feature_importances(nodes, vals, n_trees: int, d: int, is_reg: bool, criterion: int) -> np.ndarray:
     """sklearn's ``feature_importances_`` (mean decrease in impurity) of trees rooted at nodes
     0 .. n_trees-1 of a pool: float64 [d].

@@ -64,9 +64,9 @@ import torch
 
 from ..engine import faults
 from ..engine.jobs import Job, json_safe
-from ..engine.service import (Controller, Runner, attach_model, candidate_costs, job_plan, job_seed, pick_refit,
-                              plan_slices, presize_for_job, publish_results, refit_model, run_slice,
-                              should_recut)
+from ..engine.service import (Controller, Runner, attach_model, attach_permutation, candidate_costs, job_plan,
+                              job_seed, pick_refit, plan_slices, presize_for_job, publish_results, refit_model,
+                              refit_with_permutation, run_slice, should_recut)
 from ..models.base import family_of, is_classifier
 from ..utils.log import get_logger
 from . import data as pdata
@@ -556,9 +556,12 @@ class WorkerCore:
         msg = self.job_msg(a["seq"])
         dd = self.dataset(msg, ctl)
         t0 = time.perf_counter()
-        model = refit_model(msg["plan"], msg["params"][a["candidate"]], dd)
+        model, entry = refit_with_permutation(msg["plan"], msg["params"], dd, a["candidate"], msg["seed"])
         path = _save_model(ctl, msg, a["candidate"], model) if model is not None else None
-        return {"model_path": path, "wall": time.perf_counter() - t0}
+        out = {"model_path": path, "wall": time.perf_counter() - t0}
+        if entry is not None:   # train_params["permutation_importance"]: the winner's holdout importances
+            out["permutation_importance"] = entry
+        return out
 
 
 def _save_model(ctl, msg, cand: int, model) -> Optional[str]:
@@ -1521,6 +1524,9 @@ class DistributedRunner(Runner):
             return
         if kind == "refit":
             js.refit_inflight = False
+            if out.get("permutation_importance") and js.refit_candidate >= 0:
+                attach_permutation(self.ctl, js.job, js.done.get(js.held, []), js.refit_candidate,
+                                   out["permutation_importance"])
             self._finish_job(js, out.get("model_path"))
             return
         # slice

@@ -95,6 +95,14 @@ OobArgs = _i64_struct(
      "t0", "t1", "rows", "n_rows", "depth_cap", "out", "out_pred", "out_cnt", "toptab"],
 )
 
+# csrc/kernels/predict.hip PermArgs (permutation-importance statistics of one kept fit)
+PermArgs = _i64_struct(
+    "PermArgs",
+    ["Xb", "ld", "d", "nodes", "node_val", "VC", "is_reg", "n_classes", "fit_tree_off", "fit_row_off", "t0", "t1",
+     "rows", "n_rows", "depth_cap", "perm", "K", "features", "F", "ycls", "yreg", "part", "out", "out_pred",
+     "out_walked", "toptab", "no_skip"],
+)
+
 # csrc/kernels/lr_mfma.hip argument blocks (MFMA logistic-regression objective)
 LrFwdArgs = _i64_struct(
     "LrFwdArgs",
@@ -156,6 +164,8 @@ def cpu_lib() -> ctypes.CDLL:
             lib.dml_cpu_forest_oob.argtypes = [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i32, c_i32, c_vp,
                                                c_i64, c_i32, c_vp, c_vp, c_vp]
             lib.dml_boot_weight_oob.argtypes = [c_vp, ctypes.c_uint32, c_vp]
+            lib.dml_cpu_forest_perm.argtypes = [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_i64,
+                                                c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
             lib.dml_cpu_bin.argtypes = [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64]
             lib.dml_cpu_svm_sizeof_prob.restype = c_i32
             lib.dml_cpu_svm_smo.argtypes = [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]
@@ -209,6 +219,11 @@ def hip_lib() -> ctypes.CDLL:
                 raise RuntimeError("OobArgs layout mismatch between HIP library and Python")
             lib.dml_forest_oob.restype = c_i32
             lib.dml_forest_oob.argtypes = [ctypes.POINTER(OobArgs), c_vp]
+            lib.dml_perm_sizeof_args.restype = c_i32
+            if lib.dml_perm_sizeof_args() != ctypes.sizeof(PermArgs):
+                raise RuntimeError("PermArgs layout mismatch between HIP library and Python")
+            lib.dml_forest_perm.restype = c_i32
+            lib.dml_forest_perm.argtypes = [ctypes.POINTER(PermArgs), c_vp]
             lib.dml_bin.restype = c_i32
             lib.dml_bin.argtypes = [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp]
             _register_optional(lib)
