@@ -132,16 +132,59 @@ __global__ __launch_bounds__(64 * WAVES) void k_knn(const float* __restrict__ X,
 
 // ---- squared-L2 on the matrix cores ---------------------------------------------------
 // ||q - r||^2 = ||q||^2 + ||r||^2 - 2 q.r with the dot products on MFMA
-// (v_mfma_f32_32x32x16_bf16, bf16x3: x = hi + lo, q.r ~ hi.hi + hi.lo + lo.hi, ~2^-16
-// relative): a workgroup owns 32 queries (4 groups of QPW, one per wave) and streams the
-// reference rows 128 at a time -- each wave multiplies the 32 queries by its 32
-// references into a 32x32 accumulator tile, the tile goes to LDS as distances, and each
-// wave then merges its 8 queries' rows of the 32x128 block into their running top-64
-// exactly as the scalar kernel does.  The MFMA distances only SELECT candidates: the
-// final top-64 of every query is re-ranked by the exact f32 sum of (x - q)^2 in feature
-// order -- the scalar kernel's own arithmetic -- so results are those of ``k_knn<0>``
-// whenever the true K nearest lie in the approximate 64 nearest (the host uses this
-// path for K <= 32: a >= 32-row margin for the 2^-16 selection error).
+// (v_mfma_f32_32x32x16_bf16, bf16x3: x = hi + lo, q.r ~ hi.hi + hi.lo + lo.hi): a
+// workgroup owns 32 queries (4 groups of QPW, one per wave) and streams the reference
+// rows 128 at a time -- each wave multiplies the 32 queries by its 32 references into a
+// 32x32 accumulator tile, the tile goes to LDS as distances, and each wave then merges
+// its 8 queries' rows of the 32x128 block into their running top-64 exactly as the scalar
+// kernel does.  The MFMA distances only SELECT candidates: the final top-64 of every query
+// is re-ranked by the exact f32 sum of (x - q)^2 over the raw X in feature order -- the
+// scalar kernel's own arithmetic -- so a query's result is that of ``k_knn<0>`` whenever
+// its true K nearest were among the 64 selected.  The kernel PROVES that per query or
+// raises the query's flag, and the host sends flagged queries through ``k_knn<0>``.
+//
+// Operands.  The host centres the table, a = float32(x - column mean) (distances do not
+// move; the error below scales with the centred norms), splits a = ah + al + ar with
+// ah = bf16(a), al = bf16(a - ah), and stores rn = float32(|a|^2).  Query norms come from
+// the same rn, so qn + rn - 2 q.r lives in one coordinate system.
+//
+// Error of the approximate distance A(q, r) against D = ||x_q - x_r||^2, rows a (query),
+// b (reference), all norms centred, u = 2^-24:
+//  * hi/lo truncation: round-to-nearest bf16 gives |a - ah| <= 2^-9 |a| per component, so
+//    |al| <= 2^-9 (1 + 2^-9) |a| and |ar| <= 2^-18 |a|.  The dot product drops
+//    ar.b + (ah + al).br + al.bl (the lo.lo term); by Cauchy-Schwarz each is at most
+//    2^-18 (1 + 2^-8) |a||b|:                                   3 * 2^-18 (1 + 2^-7) |a||b|
+//  * fp32 accumulation: bf16 x bf16 products are exact in fp32; the 3 * 16 * ks_n of them
+//    are summed in an order the hardware does not document.  Charging every addition a
+//    relative 2u (round-to-nearest or truncation) and rounding the count up to 64 * ks_n,
+//    with sum |terms| <= (1 + 2^-7) |a||b|:              64 ks_n * 2^-23 (1 + 2^-6) |a||b|
+//    Both enter the distance doubled:
+//        c1 = 2 (3 * 2^-18 (1 + 2^-7) + 64 ks_n 2^-23 (1 + 2^-6))
+//  * rn: one fp32 rounding of |a|^2 and of |b|^2 (the float64 sum is far below that):
+//                                                                      u (|a|^2 + |b|^2)
+//  * final sum fl(fl(qn + rn) - 2 acc): u (|a|^2 + |b|^2) for the inner rounding and
+//    u (|a| + |b|)^2 <= 2u (|a|^2 + |b|^2) for the outer one; the clamp at 0 only moves
+//    the value towards D >= 0:                                        3u (|a|^2 + |b|^2)
+//  * centring: a is the fp32 rounding of x - mean, |a - (x - mean)| <= u |a| per
+//    component, so ||a - b||^2 differs from D by at most 2u (|a| + |b|)^2 (1 + u):
+//                                                                     4u (|a|^2 + |b|^2)
+//        c2 = 8u = 2^-21
+//  The host widens both by (1 + 2^-5) for the second-order terms left out above and for
+//  the fp32 evaluation of the bound, and passes c1, c2 and R = max_r |b| (rounded up):
+//        eps(q) = c1 |a| R + c2 (|a|^2 + R^2)  >=  |A(q, r) - D(q, r)|  for every row r.
+//  (Bounds assume no fp32 underflow or overflow in a^2; an overflowing bound is inf or
+//  NaN and flags the query.)
+//
+// Certificate.  Let a64 be the largest approximate distance among the 64 retained rows
+// and dK the K-th exact (fp32, re-ranked) distance.  A valid row that was not retained
+// has A >= a64, hence D >= a64 - eps, and its fp32 distance as ``k_knn<0>`` computes it --
+// d roundings of the fma chain, one of each difference, all terms non-negative -- is at
+// least D (1 - (d + 2) u).  So when
+//        dK < (a64 - eps(q)) (1 - (d + 6) u)        [4u more for evaluating this line]
+// every unretained row sorts strictly after the K-th retained one (strict: an unseen
+// exact tie with a lower row id cannot hide) and the K results are exactly those of
+// ``k_knn<0>``.  The same holds when fewer than 64 valid rows exist (all were retained).
+// Every other query gets flag 1.
 //
 // Operand layout (built once per dataset, models/neighbors.py): XHL = [2][KS][npad][16]
 // bf16 (hi, lo planes; 16-feature K-steps; row-padded to 128 with zeros), so lane l of
@@ -157,11 +200,13 @@ __device__ __forceinline__ bf16x8 ld8(const __bf16* p) { return *reinterpret_cas
 
 template <int KS>   // K-steps held in registers (0: stream the query operand from cache)
 __global__ __launch_bounds__(256) void k_knn_l2_mfma(const __bf16* __restrict__ XHL, int64_t npad, int ks_n,
-                                                     const float* __restrict__ rn, const float* __restrict__ X,
-                                                     int64_t n, int64_t d, const uint8_t* __restrict__ roles,
+                                                     const float* __restrict__ rn, float rmax, float c1, float c2,
+                                                     const float* __restrict__ X, int64_t n, int64_t d,
+                                                     const uint8_t* __restrict__ roles,
                                                      const int32_t* __restrict__ qrow,
                                                      const int32_t* __restrict__ qsplit, int32_t K,
-                                                     float* __restrict__ out_d, int32_t* __restrict__ out_i) {
+                                                     float* __restrict__ out_d, int32_t* __restrict__ out_i,
+                                                     int32_t* __restrict__ out_flag) {
   __shared__ float Dl[MQ * DL_STRIDE];
   __shared__ float qn_s[MQ];
   const int lane = lane_id();
@@ -184,10 +229,7 @@ __global__ __launch_bounds__(256) void k_knn_l2_mfma(const __bf16* __restrict__ 
   }
   if (threadIdx.x < MQ) {
     const int qq = qrow[q0 + threadIdx.x];
-    float acc = 0.f;
-    if (qq >= 0)
-      for (int64_t f = 0; f < d; ++f) { const float x = X[(int64_t)qq * d + f]; acc = __builtin_fmaf(x, x, acc); }
-    qn_s[threadIdx.x] = acc;
+    qn_s[threadIdx.x] = qq >= 0 ? rn[qq] : 0.f;   // the centred norm the operands were built from
   }
   // merge-side state: this wave's QPW queries
   const int64_t group = (int64_t)blockIdx.x * WAVES + wave;
@@ -251,6 +293,7 @@ __global__ __launch_bounds__(256) void k_knn_l2_mfma(const __bf16* __restrict__ 
     const int64_t slot = group * QPW + i;
     const int q = qrow[slot];
     if (q < 0) continue;
+    const uint64_t far = dml::wave::bcast(top[i], 63);   // kInf: fewer than 64 valid rows, all retained
     uint64_t key = kInf;
     if (top[i] != kInf) {
       const int64_t row = (int64_t)(uint32_t)top[i];
@@ -265,6 +308,15 @@ __global__ __launch_bounds__(256) void k_knn_l2_mfma(const __bf16* __restrict__ 
     if (lane < K) {
       out_d[slot * K + lane] = key == kInf ? __builtin_inff() : __builtin_bit_cast(float, (uint32_t)(key >> 32));
       out_i[slot * K + lane] = key == kInf ? -1 : (int32_t)(uint32_t)key;
+    }
+    // certificate (header comment): flag the query unless its K results are proven exact
+    if (far != kInf) {
+      const float qn = qn_s[wave * QPW + i];
+      const float eps = c1 * rmax * __builtin_sqrtf(qn) + c2 * (qn + rmax * rmax);
+      const float a64 = __builtin_bit_cast(float, (uint32_t)(far >> 32));
+      const float dK = __builtin_bit_cast(float, (uint32_t)(dml::wave::bcast(key, K - 1) >> 32));
+      const float lim = (a64 - eps) * (1.f - (float)(d + 6) * 0x1p-24f);
+      if (lane == 0 && !(dK < lim)) out_flag[slot] = 1;
     }
   }
 }
@@ -289,23 +341,28 @@ extern "C" int dml_knn(const float* X, const float* XT, int64_t n, int64_t d, co
 
 extern "C" int dml_knn_qpw() { return QPW; }
 
-// Squared-L2 search on the matrix cores (K <= 64; exact when the true K nearest are among
-// the approximate 64 nearest -- the host keeps K <= 32).  XHL: [2][ks_n][npad][16] bf16,
-// npad % 128 == 0 and >= n; rn: [n] squared row norms; qrow/qsplit: [nq_groups * 8] with
-// nq_groups % 4 == 0 (a workgroup = 4 groups; padding groups use qrow -1).
-extern "C" int dml_knn_l2_mfma(const void* XHL, int64_t npad, int32_t ks_n, const float* rn, const float* X, int64_t n,
-                               int64_t d, const uint8_t* roles, const int32_t* qrow, const int32_t* qsplit,
-                               int64_t nq_groups, int32_t K, float* out_d, int32_t* out_i, hipStream_t st) {
+// Squared-L2 search on the matrix cores (K <= 64).  A query whose out_flag stays 0 holds
+// exactly the results of ``dml_knn`` metric 0; the kernel sets out_flag[slot] = 1 (the
+// caller zeroes out_flag) where it cannot prove that, and the caller searches those
+// queries with ``dml_knn``.  XHL: [2][ks_n][npad][16] bf16 planes of the centred rows,
+// npad % 128 == 0 and >= n; rn: [n] squared norms of the centred rows; rmax >= the largest
+// such norm; c1, c2: constants of the error bound (header of k_knn_l2_mfma);
+// qrow/qsplit/out_flag: [nq_groups * 8] with nq_groups % 4 == 0 (a workgroup = 4 groups;
+// padding groups use qrow -1).
+extern "C" int dml_knn_l2_mfma(const void* XHL, int64_t npad, int32_t ks_n, const float* rn, float rmax, float c1,
+                               float c2, const float* X, int64_t n, int64_t d, const uint8_t* roles,
+                               const int32_t* qrow, const int32_t* qsplit, int64_t nq_groups, int32_t K, float* out_d,
+                               int32_t* out_i, int32_t* out_flag, hipStream_t st) {
   if (nq_groups == 0) return 0;
   if (K < 1 || K > 64 || nq_groups % WAVES || npad % MR || npad < n || (int64_t)ks_n * 16 < d) return 2;
   const unsigned blocks = (unsigned)(nq_groups / WAVES);
   const __bf16* x = static_cast<const __bf16*>(XHL);
   switch (ks_n) {
-    case 1: k_knn_l2_mfma<1><<<blocks, 256, 0, st>>>(x, npad, ks_n, rn, X, n, d, roles, qrow, qsplit, K, out_d, out_i); break;
-    case 2: k_knn_l2_mfma<2><<<blocks, 256, 0, st>>>(x, npad, ks_n, rn, X, n, d, roles, qrow, qsplit, K, out_d, out_i); break;
-    case 4: k_knn_l2_mfma<4><<<blocks, 256, 0, st>>>(x, npad, ks_n, rn, X, n, d, roles, qrow, qsplit, K, out_d, out_i); break;
-    case 8: k_knn_l2_mfma<8><<<blocks, 256, 0, st>>>(x, npad, ks_n, rn, X, n, d, roles, qrow, qsplit, K, out_d, out_i); break;
-    default: k_knn_l2_mfma<0><<<blocks, 256, 0, st>>>(x, npad, ks_n, rn, X, n, d, roles, qrow, qsplit, K, out_d, out_i); break;
+    case 1: k_knn_l2_mfma<1><<<blocks, 256, 0, st>>>(x, npad, ks_n, rn, rmax, c1, c2, X, n, d, roles, qrow, qsplit, K, out_d, out_i, out_flag); break;
+    case 2: k_knn_l2_mfma<2><<<blocks, 256, 0, st>>>(x, npad, ks_n, rn, rmax, c1, c2, X, n, d, roles, qrow, qsplit, K, out_d, out_i, out_flag); break;
+    case 4: k_knn_l2_mfma<4><<<blocks, 256, 0, st>>>(x, npad, ks_n, rn, rmax, c1, c2, X, n, d, roles, qrow, qsplit, K, out_d, out_i, out_flag); break;
+    case 8: k_knn_l2_mfma<8><<<blocks, 256, 0, st>>>(x, npad, ks_n, rn, rmax, c1, c2, X, n, d, roles, qrow, qsplit, K, out_d, out_i, out_flag); break;
+    default: k_knn_l2_mfma<0><<<blocks, 256, 0, st>>>(x, npad, ks_n, rn, rmax, c1, c2, X, n, d, roles, qrow, qsplit, K, out_d, out_i, out_flag); break;
   }
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }

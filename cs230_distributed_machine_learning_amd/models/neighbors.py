@@ -104,12 +104,34 @@ def knn_search_torch(X: torch.Tensor, qrows: torch.Tensor, train_rows: torch.Ten
     return torch.cat(out_d), torch.cat(out_i)
 
 
-MFMA_KMAX = 32   # the matrix-core path re-ranks 64 candidates: keep >= 32 rows of margin
+MFMA_KMAX = 32   # largest K the host sends to the matrix-core path (it re-ranks 64 candidates)
+
+# counts of the last ``knn_search_hip`` call: queries searched on the matrix cores, and how
+# many of them the kernel could not certify and the scalar kernel searched again
+last_search_stats = {"mfma_queries": 0, "fallback_queries": 0}
+
+
+def mfma_error_consts(ks: int) -> Tuple[float, float]:
+    """(c1, c2) of the matrix-core selection's error bound (derivation: the header comment of
+    ``k_knn_l2_mfma``, csrc/kernels/neighbors.hip): for centred rows a, b of norms |a|, |b|
+    ``|approx - ||q - r||^2| <= c1 |a| |b| + c2 (|a|^2 + |b|^2)``; ``ks`` 16-feature K-steps."""
+    c1 = 2.0 * (3.0 * 2.0 ** -18 * (1 + 2.0 ** -7) + 64.0 * ks * 2.0 ** -23 * (1 + 2.0 ** -6))
+    c2 = 8.0 * 2.0 ** -24
+    return c1 * (1 + 2.0 ** -5), c2 * (1 + 2.0 ** -5)
+
+
+def mfma_error_bound(qn: torch.Tensor, rmax: float, c1: float, c2: float) -> torch.Tensor:
+    """eps(q) as the kernel evaluates it from the centred squared norm ``qn`` of a query."""
+    return c1 * rmax * qn.sqrt() + c2 * (qn + rmax * rmax)
 
 
 def mfma_operands(data):
-    """bf16 hi/lo planes of X in the MFMA K-step layout [2][KS][npad][16] plus the squared
-    row norms (csrc/kernels/neighbors.hip ``dml_knn_l2_mfma``); built once per dataset."""
+    """Operands of the matrix-core search (csrc/kernels/neighbors.hip ``dml_knn_l2_mfma``),
+    built once per dataset from the CENTRED rows ``Xc = float32(X - column mean)`` (distances
+    are translation invariant; the selection error scales with the centred norms, not with
+    the table's offset from the origin): bf16 hi/lo planes of Xc in the K-step layout
+    [2][KS][npad][16], the squared norms ``rn`` of the Xc rows, the largest such norm
+    ``rmax`` (rounded up) and the constants of the error bound (``mfma_error_consts``)."""
     ops = getattr(data, "_knn_mfma_ops", None)
     if ops is None:
         X = data.X
@@ -118,25 +140,34 @@ def mfma_operands(data):
         if ks <= 8:
             ks = 1 << (ks - 1).bit_length()   # register-resident query operand: 1/2/4/8 K-steps
         npad = -(-n // 128) * 128
+        Xd = X.double()
+        Xc = (Xd - Xd.mean(0, keepdim=True)).float() if n else X
+        del Xd
         Xp = torch.zeros((npad, ks * 16), dtype=torch.float32, device=X.device)
-        Xp[:n, :d] = X
+        Xp[:n, :d] = Xc
         hi = Xp.to(torch.bfloat16)
         lo = (Xp - hi.float()).to(torch.bfloat16)
         xhl = torch.stack([hi, lo]).view(2, npad, ks, 16).transpose(1, 2).contiguous()
-        rn = (X.double() ** 2).sum(1).float().contiguous()
-        ops = (xhl, npad, ks, rn)
+        rn64 = (Xc.double() ** 2).sum(1)
+        rn = rn64.float().contiguous()
+        rmax = float(rn64.max().sqrt()) * (1 + 2.0 ** -20) if n else 0.0
+        ops = (xhl, npad, ks, rn, rmax, *mfma_error_consts(ks))
         data._knn_mfma_ops = ops
     return ops
 
 
 def knn_search_hip(data, splits: List[int], K: int, metric: int, p: float) -> Dict[int, Tuple[torch.Tensor, torch.Tensor]]:
     """One kernel launch for all test rows of all ``splits``: squared L2 with K <= 32 on the
-    matrix cores (exact re-rank of an MFMA-selected top-64), every other metric on the
-    scalar streaming kernel."""
+    matrix cores, every other metric on the scalar streaming kernel.  The matrix-core kernel
+    re-ranks an approximately selected top-64 exactly and flags every query for which it
+    cannot prove that selection sufficient; flagged queries are searched again by the scalar
+    kernel, so the result is the scalar kernel's, bit for bit, on any data
+    (``last_search_stats`` counts both)."""
     lib = native.hip_lib()
     qpw = int(lib.dml_knn_qpw())
     dev = data.device
     use_mfma = metric == M_L2 and K <= MFMA_KMAX and os.environ.get("DML_KNN_MFMA", "1") != "0"
+    last_search_stats.update(mfma_queries=0, fallback_queries=0)
     qr, qs, spans = [], [], {}
     off = 0
     for s in splits:
@@ -156,18 +187,36 @@ def knn_search_hip(data, splits: List[int], K: int, metric: int, p: float) -> Di
     groups = qrow.numel() // qpw
     out_d = torch.empty((qrow.numel(), K), dtype=torch.float32, device=dev)
     out_i = torch.empty((qrow.numel(), K), dtype=torch.int32, device=dev)
+    def scalar(qrow, qsplit, out_d, out_i):
+        rc = lib.dml_knn(native.ptr(data.X), native.ptr(data.feature_major()), data.n, data.d, native.ptr(data.roles),
+                         native.ptr(qrow), native.ptr(qsplit), qrow.numel() // qpw, metric,
+                         float(p if math.isfinite(p) else 0.0), K, native.ptr(out_d), native.ptr(out_i),
+                         native.stream_handle(dev))
+        if rc:
+            raise RuntimeError(f"dml_knn failed (rc={rc})")
+
     if use_mfma:
-        xhl, npad, ks, rn = mfma_operands(data)
-        rc = lib.dml_knn_l2_mfma(native.ptr(xhl), npad, ks, native.ptr(rn), native.ptr(data.X), data.n, data.d,
-                                 native.ptr(data.roles), native.ptr(qrow), native.ptr(qsplit), groups, K,
-                                 native.ptr(out_d), native.ptr(out_i), native.stream_handle(dev))
+        xhl, npad, ks, rn, rmax, c1, c2 = mfma_operands(data)
+        flags = torch.zeros((qrow.numel(),), dtype=torch.int32, device=dev)   # 1: selection not certified
+        rc = lib.dml_knn_l2_mfma(native.ptr(xhl), npad, ks, native.ptr(rn), rmax, c1, c2, native.ptr(data.X), data.n,
+                                 data.d, native.ptr(data.roles), native.ptr(qrow), native.ptr(qsplit), groups, K,
+                                 native.ptr(out_d), native.ptr(out_i), native.ptr(flags), native.stream_handle(dev))
+        if rc:
+            raise RuntimeError(f"dml_knn_l2_mfma failed (rc={rc})")
+        # uncertified queries go through the scalar kernel, by whole groups of ``qpw`` (a group
+        # shares one split; its certified members come out the same either way)
+        last_search_stats["mfma_queries"] = int(sum(m for _, m in spans.values()))
+        last_search_stats["fallback_queries"] = int(flags.sum())   # the search's one host read
+        if last_search_stats["fallback_queries"]:
+            redo = torch.nonzero(flags.view(groups, qpw).any(1)).flatten()
+            fd = torch.empty((redo.numel() * qpw, K), dtype=torch.float32, device=dev)
+            fi = torch.empty((redo.numel() * qpw, K), dtype=torch.int32, device=dev)
+            scalar(qrow.view(groups, qpw)[redo].flatten().contiguous(),
+                   qsplit.view(groups, qpw)[redo].flatten().contiguous(), fd, fi)
+            out_d.view(groups, qpw, K)[redo] = fd.view(-1, qpw, K)
+            out_i.view(groups, qpw, K)[redo] = fi.view(-1, qpw, K)
     else:
-        XT = data.feature_major()
-        rc = lib.dml_knn(native.ptr(data.X), native.ptr(XT), data.n, data.d, native.ptr(data.roles), native.ptr(qrow),
-                         native.ptr(qsplit), groups, metric, float(p if math.isfinite(p) else 0.0), K,
-                         native.ptr(out_d), native.ptr(out_i), native.stream_handle(dev))
-    if rc:
-        raise RuntimeError(f"dml_knn failed (rc={rc})")
+        scalar(qrow, qsplit, out_d, out_i)
     return {s: (out_d[o:o + m], out_i[o:o + m].long()) for s, (o, m) in spans.items()}
 
 
