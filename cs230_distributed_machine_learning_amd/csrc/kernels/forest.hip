@@ -85,6 +85,11 @@ template <int MODE> constexpr int block_nt() { return MODE == 1 ? DML_BLOCK_NT :
 #ifndef DML_PART_KEEP
 #define DML_PART_KEEP 2        // block-tier partition: rounds whose row ids pass 1 keeps in registers (0/1/2: 1.018/1.014/1.009 s sweep build, r5 e6)
 #endif
+#ifndef DML_PART_STRAIGHT
+// block-tier partition, pass 1: 1 compiles a round as straight-line code (all its loads issued,
+// then the ballots); 0: the per-position stash / gather branch (A/B builds; docs/PARTITION_LOADS.md)
+#define DML_PART_STRAIGHT 1
+#endif
 #ifndef DML_NODES_WPE_WAVE
 #define DML_NODES_WPE_WAVE 4   // wave tier (binary): 2 / 3 / 5 / 6 measured slower (ROUND3.md)
 #endif
@@ -1765,6 +1770,63 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
     for (int q = 0; q < (KR > 0 ? KR : 1); ++q)
 #pragma unroll
       for (int u = 0; u < U; ++u) rk[q][u] = 0u;
+#if DML_PART_STRAIGHT
+    // One round of pass 1 as straight-line code.  STASH (the split position is in the stash) and
+    // KEEP (the row ids stay in registers for pass 2) are compile-time: a wave-uniform run-time
+    // branch around each load becomes a scalar branch per position, and the code after it waits
+    // with vmcnt(0) -- one memory round trip per position instead of one per round.  Every load
+    // is clamped and unconditional, the stash words go out before the row ids (vmcnt retires in
+    // issue order: the ballots wait for the words only and the kept row ids stay in flight), and
+    // the word's shift and mask stand with the ballots, behind the last load.  On the gather
+    // path the U row ids go out together, then the U byte gathers.
+    auto round1 = [&](auto Sc, auto Kc, int p0, uint32_t (&keep)[U]) {
+      constexpr bool STASH = decltype(Sc)::value, KEEP = decltype(Kc)::value;
+      int pc[U];
+      uint32_t bv[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) pc[u] = min(p0 + u * NT + tid, cnt - 1);
+      if constexpr (STASH) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if constexpr (PLANES) bv[u] = *plane_word(bpl, pc[u]);   // one coalesced dword per lane
+          else bv[u] = c.bscr[(on.start + pc[u]) * 16 + bjs];
+        }
+        if constexpr (KEEP)
+#pragma unroll
+          for (int u = 0; u < U; ++u) keep[u] = rows[pc[u]];
+      } else {
+        uint32_t r[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) r[u] = rows[pc[u]];
+#pragma unroll
+        for (int u = 0; u < U; ++u) bv[u] = c.Xb[(int64_t)(r[u] & c.rmask) * c.ld + fsplit];
+        if constexpr (KEEP)
+#pragma unroll
+          for (int u = 0; u < U; ++u) keep[u] = r[u];
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int p = p0 + u * NT + tid;
+        const uint32_t b = (STASH && PLANES) ? ((bv[u] >> bsh) & 0xFFu) : bv[u];
+        // `&`, not `&&`: behind a short-circuit branch the compiler sinks the position's load
+        // into the p < cnt side and waits for it there with vmcnt(0)
+        const uint64_t m = __ballot((int)(p < cnt) & (int)((int)b <= bsplit));
+        if (lane == 0 && p - lane < cnt) lflag[(p - lane) >> 6] = m;
+      }
+    };
+    auto pass1 = [&](auto Sc) {
+      int p0 = 0;
+#pragma unroll
+      for (int q = 0; q < KR; ++q)
+        if (p0 < cnt) {
+          round1(Sc, std::true_type{}, p0, rk[q]);
+          p0 += U * NT;
+        }
+      for (; p0 < cnt; p0 += U * NT) round1(Sc, std::false_type{}, p0, rk[0]);
+    };
+    if (bjs >= 0) pass1(std::true_type{});
+    else pass1(std::false_type{});
+#else
     for (int p0 = 0, q = 0; p0 < cnt; p0 += U * NT, ++q) {
       uint32_t bv[U];
 #pragma unroll
@@ -1788,6 +1850,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
         if (lane == 0 && p - lane < cnt) lflag[(p - lane) >> 6] = m;
       }
     }
+#endif
     __syncthreads();
     // exclusive prefix of the groups' left counts: thread t owns groups [gpt t, gpt (t + 1)),
     // gpt = ceil(ngrp / NT) of them (8 at 65 536 rows and 128 threads), so no group of a node
