@@ -763,6 +763,342 @@ __global__ __launch_bounds__(256) void k_perm_reduce(const T* __restrict__ part,
   out[j] = s;
 }
 
+// ---- one-way partial dependence of a kept fit over its training rows -------------------------
+// For feature f (grid.y, a slot of features[]) and grid point g, every row is predicted from its
+// own bins except that feature f's bin is sub_bins[slot][g] -- the same for every row, so it is
+// read once per block, not gathered -- and the values (k_predict_cls's out_proba / k_predict_reg's
+// out_pred, bit for bit) are summed over the rows.  The block shape and the hit-skip are the
+// permutation kernels'; the skip test is an interval: the baseline walk of a group of U trees
+// also records the bins [lo, hi] of feature f over which no slot of the group changes its leaf
+// (lo: the largest split + 1 among the f-nodes where the row went right, hi: the smallest split
+// among those where it went left; the row's own bin lies inside), and a grid point whose bin is
+// inside adds the baseline leaves' values without walking.  Every slot adds the same value in
+// tree order whether it was walked again or not.  ../runtime/forest_pd_cpu.cpp is the host twin.
+struct PdArgs {
+  int64_t Xb, ld, d;
+  int64_t nodes, node_val, VC, is_reg, n_classes;
+  int64_t fit_tree_off;  // int32[2] device: the fit's pool trees [t0, t1)
+  int64_t fit_row_off;   // int64[2] device: {0, n_rows}
+  int64_t t0, t1;
+  int64_t rows, n_rows;  // int32[n_rows]: dataset row ids
+  int64_t depth_cap;     // <= 0: whole trees
+  int64_t features, F;   // int32 [F]: feature ids, or -1 (the baseline slot)
+  int64_t sub_bins, Gmax;   // uint8 [F][Gmax]: the bins to substitute
+  int64_t n_grid;        // int32 [F]: slot s uses sub_bins[s][0 .. n_grid[s])
+  int64_t n_targets, c0; // the values summed: classes [c0, c0 + n_targets) (regression: 1, 0)
+  int64_t part, f_chunk; // scratch double [blocks][f_chunk][Gmax][n_targets]: the slots are launched
+                         // f_chunk at a time, so the partials stay within what the caller allows
+  int64_t out;           // double [F][Gmax][n_targets]: the block partials summed in block order
+  int64_t out_rows;      // optional float [F][Gmax][n_rows][n_targets]: the per-row values
+  int64_t out_walked;    // optional uint64 [F]: (row, tree, grid point) slots walked a second time
+  int64_t toptab;        // NodeRec[t1][kTopSlots] scratch or 0
+  int64_t no_skip;       // A/B: walk every tree again for every grid point
+};
+
+struct PdTail {   // what the partial-dependence kernels take besides the predict block
+  const int32_t* features;
+  const uint8_t* sub;
+  const int32_t* n_grid;
+  double* part;
+  float* rows_out;
+  unsigned long long* walked;
+  int Gmax, Fc, f0, NT, c0, cap, no_skip;
+};
+
+// leaves_perm_u's recording walk, which also narrows [lo, hi] at every visited node on feature f
+template <int kPredU>
+__device__ __forceinline__ void leaves_pd_u(const NodeRec* __restrict__ nodes, const uint8_t* __restrict__ xr, int t0,
+                                            int u_n, int (&leaf)[kPredU], int cap, const NodeRec* top, int f,
+                                            uint32_t& hit, int& lo, int& hi) {
+  NodeRec nr[kPredU];
+  int sl[kPredU];
+#pragma unroll
+  for (int u = 0; u < kPredU; ++u) {
+    leaf[u] = t0 + u;
+    sl[u] = 0;
+    nr[u] = u < u_n ? (top ? top[u * kTopSlots] : nodes[leaf[u]]) : NodeRec{-1, -1};
+  }
+  for (int steps = 0; steps < cap; ++steps) {
+    bool any = false;
+#pragma unroll
+    for (int u = 0; u < kPredU; ++u) any |= nr[u].split >= 0;
+    if (!any) break;
+    const bool in_top = top && steps + 1 < kTopLv;
+#pragma unroll
+    for (int u = 0; u < kPredU; ++u) {
+      if (nr[u].split >= 0) {
+        const int feat = nr[u].split >> 8, thr = nr[u].split & 255;
+        const int b = xr[feat] > thr ? 1 : 0;
+        if (feat == f) {
+          hit |= 1u << u;
+          lo = b ? max(lo, thr + 1) : lo;
+          hi = b ? hi : min(hi, thr);
+        }
+        leaf[u] = nr[u].left + b;
+        if (in_top) {
+          sl[u] = 2 * sl[u] + 1 + b;
+          nr[u] = top[u * kTopSlots + sl[u]];
+        } else {
+          nr[u] = nodes[leaf[u]];
+        }
+      }
+    }
+  }
+}
+
+// block sum of one double per thread in a fixed order: lanes by xor-shuffle, lane 0 of wave w
+// leaves it in red[w * stride]; the caller adds the four waves ascending after a barrier
+__device__ __forceinline__ void pd_wave_sum(double s, double* red, int stride) {
+  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+  if ((threadIdx.x & 63) == 0) red[(threadIdx.x >> 6) * stride] = s;
+}
+
+__device__ __forceinline__ void pd_count_walked(const PdTail& e, int fs, int nw) {
+  if (!e.walked) return;
+  for (int off = 32; off >= 1; off >>= 1) nw += __shfl_xor(nw, off);
+  if ((threadIdx.x & 63) == 0 && nw) atomicAdd(e.walked + fs, (unsigned long long)nw);
+}
+
+template <int MAXC, int kPredU>
+__global__ __launch_bounds__(256) void k_pd_cls(PredictArgs a, PdTail e) {
+  constexpr int KC = perm_chunk(MAXC);
+  extern __shared__ __attribute__((aligned(16))) uint8_t xs_lds[];
+  __shared__ double red[4][KC * MAXC];
+  const int32_t* toff = GPTR(const int32_t, a.fit_tree_off);
+  const int64_t* roff = GPTR(const int64_t, a.fit_row_off);
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t r0 = roff[0], nr = roff[1] - r0;
+  if ((int64_t)blockIdx.x * 256 >= nr) return;
+  // every thread of a block with rows stays to the end (block-wide table loads and sums); a
+  // thread past the rows walks nothing and adds nothing
+  const bool live = i < nr;
+  NodeRec* top = a.toptab ? (NodeRec*)(xs_lds + top_lds_off(a)) : nullptr;
+  const uint8_t* xr = a.lds_pitch ? stage_rows(a, xs_lds, r0, nr) : nullptr;
+  const int32_t row = (GPTR(const int32_t, a.rows))[r0 + (live ? i : 0)];
+  if (!a.lds_pitch) xr = GPTR(const uint8_t, a.Xb) + (int64_t)row * a.ld;
+  const int fs = e.f0 + (int)blockIdx.y;
+  const int f = e.features[fs];
+  const int ng = e.n_grid[fs];
+  const uint8_t* subs = e.sub + (int64_t)fs * e.Gmax;
+  const int C = (int)a.n_classes;
+  const NodeRec* nodes = GPTR(const NodeRec, a.nodes);
+  const double* val = GPTR(const double, a.node_val);
+  const int tend = toff[1];
+  const float ntf = (float)(tend - toff[0]);
+  int nw = 0;
+  for (int g0 = 0; g0 < ng; g0 += KC) {
+    int sub[KC];
+#pragma unroll
+    for (int kk = 0; kk < KC; ++kk) sub[kk] = g0 + kk < ng ? subs[g0 + kk] : 0;   // uniform over the block
+    float p[KC][MAXC];
+#pragma unroll
+    for (int kk = 0; kk < KC; ++kk)
+#pragma unroll
+      for (int k = 0; k < MAXC; ++k) p[kk][k] = 0.f;
+    for (int t = toff[0]; t < tend; t += kPredU) {
+      int base[kPredU];
+      const int u_all = min(kPredU, tend - t), u_n = live ? u_all : 0;
+      if (top) load_top<kPredU>(a, top, t, u_all);
+      uint32_t hit = 0;
+      int lo = 0, hi = 255;
+      leaves_pd_u<kPredU>(nodes, xr, t, u_n, base, e.cap, top, f, hit, lo, hi);
+      if (e.no_skip) hit = (1u << u_n) - 1u;
+      // narrow class counts: the baseline leaves' fractions are computed once per group and added
+      // as they are for every grid point that keeps the leaf (the same floats, so the same sums)
+      constexpr bool kKeep = MAXC <= 4;
+      float bc[kKeep ? kPredU : 1][MAXC];
+      uint32_t bok = 0;
+      if (kKeep) {
+#pragma unroll
+        for (int u = 0; u < kPredU; ++u) {
+          if (u >= u_n) continue;
+          const double* v = val + (int64_t)base[u] * a.VC;
+          double W = 0.0;
+#pragma unroll
+          for (int k = 0; k < MAXC; ++k)
+            if (k < C) W += v[k];
+          if (W > 0.0) {
+            const double inv = 1.0 / W;
+            bok |= 1u << u;
+#pragma unroll
+            for (int k = 0; k < MAXC; ++k)
+              if (k < C) bc[kKeep ? u : 0][k] = (float)(v[k] * inv);
+          }
+        }
+      }
+#pragma unroll
+      for (int kk = 0; kk < KC; ++kk) {
+        if (g0 + kk >= ng) break;
+        int lk[kPredU];
+#ifdef DML_PD_PLAIN_SKIP   // A/B build: the permutation kernels' test, the row's own bin alone
+        const bool inside = sub[kk] == (f >= 0 ? xr[f] : 0);
+#else
+        const bool inside = sub[kk] >= lo && sub[kk] <= hi;
+#endif
+        const uint32_t m = (!inside || e.no_skip) ? hit : 0u;
+        if (m) {
+          uint32_t none = 0;
+          leaves_perm_u<kPredU, false>(nodes, xr, t, u_n, lk, e.cap, top, m, f, sub[kk], none);
+          nw += __popc(m);
+        }
+        // accumulate in tree order (bit-identical to the predict kernels and the host twin)
+#pragma unroll
+        for (int u = 0; u < kPredU; ++u) {   // no break: a constant trip count keeps lk / base in registers
+          if (u >= u_n) continue;
+          if (kKeep && !((m >> u) & 1u)) {
+            if ((bok >> u) & 1u) {
+#pragma unroll
+              for (int k = 0; k < MAXC; ++k)
+                if (k < C) p[kk][k] += bc[kKeep ? u : 0][k];
+            }
+            continue;
+          }
+          const double* v = val + (int64_t)(((m >> u) & 1u) ? lk[u] : base[u]) * a.VC;
+          double W = 0.0;
+#pragma unroll
+          for (int k = 0; k < MAXC; ++k)
+            if (k < C) W += v[k];
+          if (W > 0.0) {
+            const double inv = 1.0 / W;
+#pragma unroll
+            for (int k = 0; k < MAXC; ++k)
+              if (k < C) p[kk][k] += (float)(v[k] * inv);
+          }
+        }
+      }
+    }
+    // the values of this chunk's grid points: k_predict_cls's out_proba for classes [c0, c0 + NT)
+#pragma unroll
+    for (int kk = 0; kk < KC; ++kk) {
+      const bool on = live && g0 + kk < ng;
+#pragma unroll
+      for (int k = 0; k < MAXC; ++k) {
+        if (k < e.c0 || k >= e.c0 + e.NT) continue;   // uniform
+        const float q = p[kk][k] / ntf;
+        if (on && e.rows_out)
+          e.rows_out[(((int64_t)fs * e.Gmax + g0 + kk) * nr + i) * e.NT + (k - e.c0)] = q;
+        pd_wave_sum(on ? (double)q : 0.0, &red[0][kk * MAXC + k], KC * MAXC);
+      }
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < KC * MAXC) {
+      const int j = threadIdx.x, kk = j / MAXC, k = j - kk * MAXC;
+      if (g0 + kk < ng && k >= e.c0 && k < e.c0 + e.NT)
+        e.part[((((int64_t)blockIdx.x * e.Fc + blockIdx.y) * e.Gmax) + g0 + kk) * e.NT + (k - e.c0)] =
+            red[0][j] + red[1][j] + red[2][j] + red[3][j];
+    }
+    __syncthreads();   // red is free for the next chunk
+  }
+  pd_count_walked(e, fs, nw);
+}
+
+template <int kPredU>
+__global__ __launch_bounds__(256) void k_pd_reg(PredictArgs a, PdTail e) {
+  constexpr int KC = 8;
+  extern __shared__ __attribute__((aligned(16))) uint8_t xs_lds[];
+  __shared__ double red[4][KC];
+  const int32_t* toff = GPTR(const int32_t, a.fit_tree_off);
+  const int64_t* roff = GPTR(const int64_t, a.fit_row_off);
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t r0 = roff[0], nr = roff[1] - r0;
+  if ((int64_t)blockIdx.x * 256 >= nr) return;
+  const bool live = i < nr;   // as in k_pd_cls: every thread stays
+  NodeRec* top = a.toptab ? (NodeRec*)(xs_lds + top_lds_off(a)) : nullptr;
+  const uint8_t* xr = a.lds_pitch ? stage_rows(a, xs_lds, r0, nr) : nullptr;
+  const int32_t row = (GPTR(const int32_t, a.rows))[r0 + (live ? i : 0)];
+  if (!a.lds_pitch) xr = GPTR(const uint8_t, a.Xb) + (int64_t)row * a.ld;
+  const int fs = e.f0 + (int)blockIdx.y;
+  const int f = e.features[fs];
+  const int ng = e.n_grid[fs];
+  const uint8_t* subs = e.sub + (int64_t)fs * e.Gmax;
+  const NodeRec* nodes = GPTR(const NodeRec, a.nodes);
+  const double* val = GPTR(const double, a.node_val);
+  const int tend = toff[1];
+  int nw = 0;
+  for (int g0 = 0; g0 < ng; g0 += KC) {
+    int sub[KC];
+#pragma unroll
+    for (int kk = 0; kk < KC; ++kk) sub[kk] = g0 + kk < ng ? subs[g0 + kk] : 0;   // uniform over the block
+    double acc[KC];
+    int nt[KC];
+#pragma unroll
+    for (int kk = 0; kk < KC; ++kk) { acc[kk] = 0.0; nt[kk] = 0; }
+    for (int t = toff[0]; t < tend; t += kPredU) {
+      int base[kPredU];
+      const int u_all = min(kPredU, tend - t), u_n = live ? u_all : 0;
+      if (top) load_top<kPredU>(a, top, t, u_all);
+      uint32_t hit = 0;
+      int lo = 0, hi = 255;
+      leaves_pd_u<kPredU>(nodes, xr, t, u_n, base, e.cap, top, f, hit, lo, hi);
+      if (e.no_skip) hit = (1u << u_n) - 1u;
+      // the baseline leaves' means, computed once per group (as k_pd_cls keeps its fractions)
+      double bq[kPredU];
+      uint32_t bok = 0;
+#pragma unroll
+      for (int u = 0; u < kPredU; ++u) {
+        if (u >= u_n) continue;
+        const double* v = val + (int64_t)base[u] * a.VC;
+        if (v[0] > 0.0) { bq[u] = v[1] / v[0]; bok |= 1u << u; }
+      }
+#pragma unroll
+      for (int kk = 0; kk < KC; ++kk) {
+        if (g0 + kk >= ng) break;
+        int lk[kPredU];
+#ifdef DML_PD_PLAIN_SKIP   // A/B build: the permutation kernels' test, the row's own bin alone
+        const bool inside = sub[kk] == (f >= 0 ? xr[f] : 0);
+#else
+        const bool inside = sub[kk] >= lo && sub[kk] <= hi;
+#endif
+        const uint32_t m = (!inside || e.no_skip) ? hit : 0u;
+        if (m) {
+          uint32_t none = 0;
+          leaves_perm_u<kPredU, false>(nodes, xr, t, u_n, lk, e.cap, top, m, f, sub[kk], none);
+          nw += __popc(m);
+        }
+#pragma unroll
+        for (int u = 0; u < kPredU; ++u) {
+          if (u >= u_n) continue;
+          if (!((m >> u) & 1u)) {
+            if ((bok >> u) & 1u) { acc[kk] += bq[u]; ++nt[kk]; }
+            continue;
+          }
+          const double* v = val + (int64_t)lk[u] * a.VC;
+          if (v[0] > 0.0) { acc[kk] += v[1] / v[0]; ++nt[kk]; }
+        }
+      }
+    }
+#pragma unroll
+    for (int kk = 0; kk < KC; ++kk) {
+      const float q = nt[kk] ? (float)(acc[kk] / nt[kk]) : 0.f;
+      const bool on = live && g0 + kk < ng;
+      if (on && e.rows_out) e.rows_out[((int64_t)fs * e.Gmax + g0 + kk) * nr + i] = q;
+      pd_wave_sum(on ? (double)q : 0.0, &red[0][kk], KC);
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < KC && g0 + (int)threadIdx.x < ng) {
+      const int kk = threadIdx.x;
+      e.part[(((int64_t)blockIdx.x * e.Fc + blockIdx.y) * e.Gmax) + g0 + kk] =
+          red[0][kk] + red[1][kk] + red[2][kk] + red[3][kk];
+    }
+    __syncthreads();   // red is free for the next chunk
+  }
+  pd_count_walked(e, fs, nw);
+}
+
+// out[f0 + s][g][k] = the block partials of slot s added in block order (one thread per entry:
+// the same sum every run); entries past a slot's n_grid are left as they are
+__global__ __launch_bounds__(256) void k_pd_reduce(const double* __restrict__ part, double* __restrict__ out,
+                                                   const int32_t* __restrict__ n_grid, int64_t blocks, int Fc, int f0,
+                                                   int Gmax, int NT) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x, FGN = (int64_t)Fc * Gmax * NT;
+  if (j >= FGN) return;
+  const int s = (int)(j / ((int64_t)Gmax * NT)), g = (int)(j / NT) % Gmax;
+  if (g >= n_grid[f0 + s]) return;
+  double acc = 0.0;
+  for (int64_t b = 0; b < blocks; ++b) acc += part[b * FGN + j];
+  out[(int64_t)f0 * Gmax * NT + j] = acc;
+}
+
 // per-fit score statistics: out[f] = {match_count or SSE, sum y, sum y^2, n}
 struct ScoreArgs {
   int64_t rows;        // int32[] row ids
@@ -1002,6 +1338,58 @@ static int launch_perm(const PermArgs* o, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
+// launch_perm's LDS layout with grid.y = a slot of features[]; the slots go f_chunk at a time, each
+// chunk's partials reduced into out before the next chunk overwrites them (one stream: in order)
+template <int U>
+static int launch_pd(const PdArgs* o, hipStream_t st) {
+  PredictArgs a{};
+  a.Xb = o->Xb; a.ld = o->ld; a.d = o->d;
+  a.nodes = o->nodes; a.node_val = o->node_val; a.VC = o->VC; a.is_reg = o->is_reg; a.n_classes = o->n_classes;
+  a.fit_tree_off = o->fit_tree_off; a.fit_row_off = o->fit_row_off; a.rows = o->rows;
+  a.F = 1; a.max_rows = o->n_rows; a.max_trees = o->t1 - o->t0;
+  a.toptab = o->toptab;
+  // stage_rows' row list and the largest block-sum table (KC * MAXC <= 64 doubles per wave)
+  constexpr size_t kStatic = 256 * sizeof(int32_t) + 4 * 64 * sizeof(double);
+  a.lds_pitch = predict_pitch(&a);
+  if ((size_t)a.lds_pitch * 256 + kStatic > 64 * 1024) a.lds_pitch = 0;
+  size_t lds = (size_t)a.lds_pitch * 256;
+  static const bool top_off = getenv("DML_PRED_NO_TOP") != nullptr;
+  const size_t lds_top = ((lds + 15) & ~(size_t)15) + (size_t)U * kTopSlots * sizeof(NodeRec);
+  if (top_off || lds_top + kStatic > 64 * 1024) a.toptab = 0;
+  if (a.toptab) {
+    k_top_fill<<<dim3((unsigned)((a.max_trees + 3) / 4), 1), 256, 0, st>>>(a);
+    lds = lds_top;
+  }
+  static const bool no_skip = getenv("DML_PD_NO_SKIP") != nullptr;
+  const int C = (int)o->n_classes;
+  const int64_t blocks = (o->n_rows + 255) / 256;
+  for (int64_t f0 = 0; f0 < o->F; f0 += o->f_chunk) {
+    const int Fc = (int)(o->F - f0 < o->f_chunk ? o->F - f0 : o->f_chunk);
+    const PdTail e{GPTR(const int32_t, o->features), GPTR(const uint8_t, o->sub_bins), GPTR(const int32_t, o->n_grid),
+                   GPTR(double, o->part), o->out_rows ? GPTR(float, o->out_rows) : nullptr,
+                   o->out_walked ? GPTR(unsigned long long, o->out_walked) : nullptr,
+                   (int)o->Gmax, Fc, (int)f0, (int)o->n_targets, (int)o->c0,
+                   o->depth_cap > 0 ? (int)o->depth_cap : 1 << 20, (no_skip || o->no_skip) ? 1 : 0};
+    const dim3 grid((unsigned)blocks, (unsigned)Fc);
+    if (o->is_reg) k_pd_reg<U><<<grid, 256, lds, st>>>(a, e);
+    else if (C <= 2) k_pd_cls<2, U><<<grid, 256, lds, st>>>(a, e);
+    else if (C <= 4) k_pd_cls<4, U><<<grid, 256, lds, st>>>(a, e);
+    else if (C <= 8) k_pd_cls<8, U><<<grid, 256, lds, st>>>(a, e);
+    else if (C <= 16) k_pd_cls<16, U><<<grid, 256, lds, st>>>(a, e);
+    else if (C <= 32) k_pd_cls<32, U><<<grid, 256, lds, st>>>(a, e);
+    else if (C <= 64) {
+      // as launch_perm: 64 class sums run the 8-wide walk (dml_forest_pd), or the leaf arrays spill
+      if constexpr (U < 16) k_pd_cls<64, U><<<grid, 256, lds, st>>>(a, e);
+      else return 5;
+    } else return 5;
+    const int64_t FGN = (int64_t)Fc * o->Gmax * o->n_targets;
+    k_pd_reduce<<<(unsigned)((FGN + 255) / 256), 256, 0, st>>>(GPTR(const double, o->part), GPTR(double, o->out),
+                                                             GPTR(const int32_t, o->n_grid), blocks, Fc, (int)f0,
+                                                             (int)o->Gmax, (int)o->n_targets);
+  }
+  return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
 // max_leaf_nodes: one lane per limited tree replays sklearn's best-first order over the
 // grown tree (forest_common.h best_first_prune); the frontier heap lives in global
 // scratch, ``cap`` entries per lane.  Trees with limit 0 are left alone.
@@ -1102,6 +1490,23 @@ int dml_forest_perm(const PermArgs* o, hipStream_t st) {
   if (u == 16 && (o->is_reg || o->n_classes <= 32)) return launch_perm<16>(o, st);
   if (u == 4) return launch_perm<4>(o, st);
   return launch_perm<8>(o, st);
+}
+
+int dml_pd_sizeof_args() { return (int)sizeof(PdArgs); }
+
+// partial-dependence sums of one kept fit over its rows (k_pd_cls / k_pd_reg, then k_pd_reduce,
+// f_chunk slots of features[] per launch)
+int dml_forest_pd(const PdArgs* o, hipStream_t st) {
+  if (o->n_rows <= 0 || o->F <= 0) return 0;
+  if (o->t1 <= o->t0 || o->t0 < 0 || o->f_chunk < 1 || o->f_chunk > 65535 || o->Gmax < 1 || !o->part || !o->out ||
+      !o->features || !o->sub_bins || !o->n_grid)
+    return 2;
+  if (o->n_targets < 1 || o->c0 < 0 || (o->is_reg ? o->n_targets != 1 || o->c0 != 0 : o->c0 + o->n_targets > o->n_classes))
+    return 2;
+  static const int u = [] { const char* e = getenv("DML_PRED_U"); return e ? atoi(e) : 8; }();
+  if (u == 16 && (o->is_reg || o->n_classes <= 32)) return launch_pd<16>(o, st);
+  if (u == 4) return launch_pd<4>(o, st);
+  return launch_pd<8>(o, st);
 }
 
 int dml_scores(ScoreArgs* a, hipStream_t st) {

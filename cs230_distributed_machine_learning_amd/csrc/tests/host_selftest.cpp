@@ -25,6 +25,9 @@ void dml_cpu_forest_apply(const uint8_t*, int64_t, int64_t, const NodeRec*, int3
 void dml_cpu_forest_free(void*);
 void dml_cpu_forest_predict(const uint8_t*, int64_t, const NodeRec*, const double*, int64_t, int64_t, int64_t,
                             const int32_t*, const int64_t*, const int32_t*, int64_t, int32_t*, float*, float*);
+void dml_cpu_forest_pd(const uint8_t*, int64_t, const NodeRec*, const double*, int64_t, int64_t, int64_t, int32_t,
+                       int32_t, const int32_t*, int64_t, int32_t, const int32_t*, int64_t, const uint8_t*, int64_t,
+                       const int32_t*, int64_t, int64_t, int32_t, int32_t, double*, double*, float*, uint64_t*);
 void dml_cpu_bin(const float*, int64_t, int64_t, const float*, uint8_t*, int64_t);
 double dml_lpt_assign(const double*, const double*, int64_t, const double*, const double*, const double*, int64_t,
                       int32_t*);
@@ -136,6 +139,28 @@ static void forest_case(bool is_reg, int crit) {
       CHECK(std::fabs(ps - 1.f) < 1e-3f);
       hits += out_cls[i] == ycls[r];
     }
+  }
+  // partial dependence of the first fit over the same rows (forest_pd_cpu.cpp), every buffer at its
+  // exact size: the baseline slot is the predict above, and a skipped walk changes no value
+  {
+    const int64_t F = 3, G = 3, NT = is_reg ? 1 : C, blocks = (R + 255) / 256;
+    const int32_t feats[F] = {-1, 0, 3}, ngrid[F] = {1, 3, 2};
+    const uint8_t sub[F * G] = {0, 0, 0, 5, 120, 250, 0, 200, 0};
+    std::vector<double> part((size_t)(blocks * F * G * NT)), sums((size_t)(F * G * NT), 0.0), sums2(sums);
+    std::vector<float> pv((size_t)(F * G * R * NT), 0.f), pv2(pv);
+    uint64_t walked[F], walked2[F];
+    dml_cpu_forest_pd(Xb.data(), d, nodes.data(), vals.data(), VC, is_reg, C, 0, 4, rows.data(), R, 0, feats, F, sub, G,
+                      ngrid, NT, 0, 8, 0, part.data(), sums.data(), pv.data(), walked);
+    dml_cpu_forest_pd(Xb.data(), d, nodes.data(), vals.data(), VC, is_reg, C, 0, 4, rows.data(), R, 0, feats, F, sub, G,
+                      ngrid, NT, 0, 8, 1, part.data(), sums2.data(), pv2.data(), walked2);
+    CHECK(pv == pv2 && sums == sums2);
+    CHECK(walked[0] == 0 && walked2[0] == (uint64_t)(4 * R) && walked2[1] == (uint64_t)(3 * 4 * R) && walked[1] < walked2[1]);
+    for (int64_t i = 0; i < R; ++i)
+      for (int64_t k = 0; k < NT; ++k)
+        CHECK(pv[i * NT + k] == (is_reg ? out_reg[i] : proba[i * C + k]));
+    double s0 = 0.0;
+    for (int64_t i = 0; i < R; ++i) s0 += pv[i * NT];
+    CHECK(std::fabs(sums[0] - s0) <= 1e-12 * std::fabs(s0));
   }
   if (is_reg) {
     std::printf("regression r2 %.3f\n", 1.0 - se / var);

@@ -52,6 +52,10 @@ class JobSpec:
     # with candidates == "all" every candidate's holdout fit computes it; "best" is one extra fit
     # after aggregation (holdout_permutation)
     permutation: Optional[Dict[str, Any]] = None
+    # train_params["partial_dependence"] as service.job_plan resolved it (RandomForest* only).  The
+    # refit computes it (service.refit_model sets FitTask.partial_dependence); here it only names
+    # the tables on which the refit will compute nothing
+    partial_dependence: Optional[Dict[str, Any]] = None
 
     def split_key(self):
         return (self.cv, self.holdout, str(self.test_size), str(self.random_state), is_classifier(self.model_type))
@@ -269,6 +273,12 @@ def run_candidates(data, spec: JobSpec, candidate_ids: Sequence[int]) -> List[Ca
                         warnings.append(PERM_SHARDED)
                     if spec.keep_models not in ("all", "best"):   # kept for the importances only
                         model = None
+                if spec.partial_dependence:
+                    from ..models.forest import PD_BINNED, PD_SHARDED
+
+                    off = PD_SHARDED if sharded else (PD_BINNED if getattr(data, "X", None) is None else None)
+                    if off and off not in warnings:
+                        warnings.append(off)
             else:
                 R["training_time"] = fit_s
             if cv_idx:
@@ -310,6 +320,30 @@ def permutation_entry(model) -> Optional[Dict[str, Any]]:
             "baseline_score": float(model["permutation_baseline_score"]),
             "scoring": meta.get("scoring"), "n_repeats": meta.get("n_repeats"),
             "random_state": meta.get("random_state")}
+
+
+PD_MODEL_KEYS = ("pd_features", "pd_grid_off", "pd_grid_values", "pd_average", "pd_rows", "pd_meta")
+
+
+def partial_dependence_entry(model) -> Optional[Dict[str, Any]]:
+    """The ``partial_dependence`` entry of a J4 result from a model that carries the arrays: per
+    computed feature its grid values [G] and its averages [n_targets][G], as plain lists."""
+    if not isinstance(model, dict) or model.get("pd_features") is None:
+        return None
+    meta = model.get("pd_meta") or {}
+    off = np.asarray(model["pd_grid_off"], dtype=np.int64)
+    grid = np.asarray(model["pd_grid_values"], dtype=np.float64)
+    avg = np.asarray(model["pd_average"], dtype=np.float64)
+    F = len(off) - 1
+    entry = {"features": [int(f) for f in model["pd_features"]],
+             "grid_values": [grid[off[j]:off[j + 1]].tolist() for j in range(F)],
+             "average": [avg[:, off[j]:off[j + 1]].tolist() for j in range(F)],
+             "n_rows": int(len(model["pd_rows"])), "grid_resolution": meta.get("grid_resolution"),
+             "percentiles": meta.get("percentiles"), "max_rows": meta.get("max_rows"),
+             "random_state": meta.get("random_state")}
+    if meta.get("warnings"):
+        entry["warnings"] = list(meta["warnings"])
+    return entry
 
 
 def holdout_permutation(data, spec: JobSpec, candidate: int) -> Optional[Dict[str, Any]]:

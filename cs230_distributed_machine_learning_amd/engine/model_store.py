@@ -30,7 +30,8 @@ import numpy as np
 _ARRAY_KEYS = ("nodes", "vals", "edges", "coef", "intercept", "X", "y", "init", "stage_offsets", "scale", "mean",
                "components", "var", "min", "max", "value", "roots", "feature_importances", "oob_rows",
                "oob_decision_function", "oob_prediction", "permutation_importances", "permutation_importances_mean",
-               "permutation_importances_std", "permutation_baseline_score", "permutation_rows")
+               "permutation_importances_std", "permutation_baseline_score", "permutation_rows", "pd_features",
+               "pd_grid_off", "pd_grid_values", "pd_average", "pd_rows")
 
 
 def save_model(model: Dict[str, Any], path: str) -> str:
@@ -158,6 +159,16 @@ class PermutationImportance:
     scoring: Optional[str] = None
     n_repeats: Optional[int] = None
     random_state: Optional[int] = None
+
+
+@dataclass
+class PartialDependence:
+    """``Predictor.partial_dependence(feature)``: sklearn's Bunch fields for ``kind="average"``."""
+
+    average: np.ndarray              # [n_targets, G]
+    grid_values: list                # [array(G)]
+    feature: int = -1
+    n_rows: Optional[int] = None     # training rows that were averaged over
 
 
 class Predictor:
@@ -344,6 +355,31 @@ class Predictor:
             rows=np.asarray(m["permutation_rows"]),
             importances=None if imp is None else np.asarray(imp, dtype=np.float64),
             scoring=meta.get("scoring"), n_repeats=meta.get("n_repeats"), random_state=meta.get("random_state"))
+
+    def partial_dependence(self, feature) -> "PartialDependence":
+        """One-way partial dependence of ``feature`` (a column position, or a name when the
+        artefact has ``feature_names``) on the fit's training rows, as the job computed it
+        (docs/PARTIAL_DEPENDENCE.md): sklearn's ``partial_dependence(..., method="brute",
+        kind="average")`` fields."""
+        m = self.model if self.kind == "forest" else {}
+        if m.get("pd_features") is None:
+            raise AttributeError(f"{self.model_type} artefact has no partial_dependence (train with "
+                                 f"train_params[\"partial_dependence\"])")
+        f = feature
+        if isinstance(f, str):
+            names = list(m.get("feature_names") or [])
+            if f not in names:
+                raise KeyError(f"no feature named {f!r} in this artefact")
+            f = names.index(f)
+        feats = [int(x) for x in np.asarray(m["pd_features"])]
+        if isinstance(f, bool) or not isinstance(f, (int, np.integer)) or int(f) not in feats:
+            raise KeyError(f"partial dependence was not computed for feature {feature!r} (computed: {feats})")
+        j = feats.index(int(f))
+        off = np.asarray(m["pd_grid_off"], dtype=np.int64)
+        return PartialDependence(
+            average=np.asarray(m["pd_average"], dtype=np.float64)[:, off[j]:off[j + 1]].copy(),
+            grid_values=[np.asarray(m["pd_grid_values"], dtype=np.float64)[off[j]:off[j + 1]].copy()],
+            feature=int(f), n_rows=int(len(m["pd_rows"])))
 
     # ---- transformers ------------------------------------------------------------------
     def transform(self, X) -> np.ndarray:

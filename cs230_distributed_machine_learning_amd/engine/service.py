@@ -105,6 +105,51 @@ def permutation_options(tp: Dict[str, Any], model_type: str, holdout: bool, job_
     return {"n_repeats": int(k), "random_state": int(rs), "scoring": scoring, "candidates": cands}
 
 
+PD_KEYS = ("features", "grid_resolution", "percentiles", "max_rows", "random_state")
+
+
+def partial_dependence_options(tp: Dict[str, Any], model_type: str) -> Optional[Dict[str, Any]]:
+    """``train_params["partial_dependence"]`` (True or a dict of ``PD_KEYS``) resolved to
+    {"features", "grid_resolution", "percentiles", "max_rows", "random_state"}; None when the job
+    does not ask.  ``features=None`` is every column, ``max_rows=None`` every training row."""
+    v = tp.get("partial_dependence")
+    if v is None or v is False:
+        return None
+    if v is True:
+        v = {}
+    if not isinstance(v, dict):
+        raise ParamError(f"train_params.partial_dependence must be true or a dict of {', '.join(PD_KEYS)}")
+    unknown = sorted(k for k in v if k not in PD_KEYS)
+    if unknown:
+        raise ParamError(f"partial_dependence: unknown key(s) {unknown}; supported: {list(PD_KEYS)}")
+    if model_type not in ("RandomForestClassifier", "RandomForestRegressor"):
+        raise ParamError(f"partial_dependence is available for RandomForestClassifier and "
+                         f"RandomForestRegressor, not {model_type}")
+    is_int = lambda x: isinstance(x, int) and not isinstance(x, bool)
+    feats = v.get("features")
+    if feats is not None:
+        if not isinstance(feats, (list, tuple)) or not feats or not all(is_int(f) and f >= 0 for f in feats) or \
+                len(set(feats)) != len(feats):
+            raise ParamError(f"partial_dependence: features must be None or a list of distinct column positions "
+                             f">= 0, got {feats!r}")
+        feats = [int(f) for f in feats]
+    res = v.get("grid_resolution", 100)
+    if not is_int(res) or res < 2:
+        raise ParamError(f"partial_dependence: grid_resolution must be an int >= 2, got {res!r}")
+    pct = v.get("percentiles", [0.05, 0.95])
+    if not isinstance(pct, (list, tuple)) or len(pct) != 2 or \
+            not all(isinstance(x, (int, float)) and not isinstance(x, bool) for x in pct) or not 0 <= pct[0] < pct[1] <= 1:
+        raise ParamError(f"partial_dependence: percentiles must be [lo, hi] with 0 <= lo < hi <= 1, got {pct!r}")
+    mr = v.get("max_rows", 50_000)
+    if mr is not None and (not is_int(mr) or mr < 1):
+        raise ParamError(f"partial_dependence: max_rows must be None or an int >= 1, got {mr!r}")
+    rs = v.get("random_state", 0)
+    if not is_int(rs) or not 0 <= rs < 2**32:
+        raise ParamError(f"partial_dependence: random_state must be an int in [0, 2**32), got {rs!r}")
+    return {"features": feats, "grid_resolution": int(res), "percentiles": [float(pct[0]), float(pct[1])],
+            "max_rows": None if mr is None else int(mr), "random_state": int(rs)}
+
+
 def job_plan(request: Dict[str, Any]) -> Dict[str, Any]:
     """Derive everything a worker needs from a J1 request."""
     md = request.get("model_details") or {}
@@ -138,6 +183,7 @@ def job_plan(request: Dict[str, Any]) -> Dict[str, Any]:
     if par == "data" and not getattr(family_of(model_type), "data_parallel", False):
         raise ParamError(f"{model_type} has no row-sharded (data-parallel) fit; use parallelism 'task'")
     perm = permutation_options(tp, model_type, bool(tp.get("holdout", True)), request.get("job_id"))
+    pd_opts = partial_dependence_options(tp, model_type)
     plan = {
         "model_type": model_type, "search_type": search_type, "candidates": cands, "cv": cv,
         "scoring": scoring, "error_score": error_score, "refit": bool(refit) if not isinstance(refit, str) else True,
@@ -152,6 +198,8 @@ def job_plan(request: Dict[str, Any]) -> Dict[str, Any]:
     }
     if perm is not None:   # a job that does not ask carries no such key
         plan["permutation_importance"] = perm
+    if pd_opts is not None:
+        plan["partial_dependence"] = pd_opts
     return plan
 
 
@@ -550,7 +598,8 @@ def run_slice(plan: Dict[str, Any], params: List[Dict[str, Any]], subtask_ids: L
     spec = JobSpec(model_type=plan["model_type"], candidates=params, cv=plan["cv"], scoring=plan["scoring"],
                    holdout=plan["holdout"], test_size=plan["test_size"], random_state=plan["random_state"],
                    error_score=plan["error_score"], keep_models="all" if keep_all else "none", seed=seed,
-                   raise_batch_errors=True, permutation=plan.get("permutation_importance"))
+                   raise_batch_errors=True, permutation=plan.get("permutation_importance"),
+                   partial_dependence=plan.get("partial_dependence"))
     received = utc_iso()
     slice_key = ",".join(str(int(c)) for c in cand_ids)
     gpu = dd.device.index if dd.is_gpu else None
@@ -724,6 +773,8 @@ def refit_model(plan: Dict[str, Any], params: Dict[str, Any], dd) -> Optional[Di
     tasks, errors = build_tasks(dd, spec, [0])
     if errors or not tasks:
         return None
+    for t in tasks:   # train_params["partial_dependence"]: computed on the refit model's own training rows
+        t.partial_dependence = plan.get("partial_dependence")
     outs = fam.run(dd, tasks, keep_models=True)
     if not outs or outs[0].model is None:
         return None
@@ -765,13 +816,19 @@ def refit_with_permutation(plan: Dict[str, Any], params: List[Dict[str, Any]], d
     return model, entry
 
 
-def attach_permutation(ctl: Controller, job: Job, results, cand: int, entry: Dict[str, Any]) -> None:
-    """The winner's importances go on its J4 result like the refit model's path (``attach_model``)."""
+def attach_entry(ctl: Controller, job: Job, results, cand: int, key: str, entry: Dict[str, Any]) -> None:
+    """An entry computed with the refit goes on the winner's J4 result like the refit model's path
+    (``attach_model``): in ``results`` when it is there, else on its published subtask."""
     for r in results:
         if r.candidate == cand and r.ok:
-            r.result["permutation_importance"] = entry
+            r.result[key] = entry
             return
-    ctl.table.update_result(job.job_id, job.subtasks[cand].subtask_id, {"permutation_importance": json_safe(entry)})
+    ctl.table.update_result(job.job_id, job.subtasks[cand].subtask_id, {key: json_safe(entry)})
+
+
+def attach_permutation(ctl: Controller, job: Job, results, cand: int, entry: Dict[str, Any]) -> None:
+    """The winner's importances go on its J4 result."""
+    attach_entry(ctl, job, results, cand, "permutation_importance", entry)
 
 
 def refit_best(ctl: Controller, job: Job, plan: Dict[str, Any], dd, best_idx: int, results=None) -> Optional[str]:
@@ -785,6 +842,11 @@ def refit_best(ctl: Controller, job: Job, plan: Dict[str, Any], dd, best_idx: in
         attach_permutation(ctl, job, results or [], best_idx, entry)
     if model is None:
         return None
+    from .executor import partial_dependence_entry
+
+    pd_entry = partial_dependence_entry(model)
+    if pd_entry is not None:   # train_params["partial_dependence"]: the refit model's own curves
+        attach_entry(ctl, job, results or [], best_idx, "partial_dependence", pd_entry)
     model["job_id"] = job.job_id
     model["subtask_id"] = job.subtasks[best_idx].subtask_id
     model["feature_names"] = list(ctl.registry.load(job.dataset_id, plan["feature_columns"],

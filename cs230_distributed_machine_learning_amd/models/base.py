@@ -32,6 +32,10 @@ class FitTask:
     # RandomForest*: {"n_repeats", "random_state", "scoring"} -- a kept fit also computes sklearn's
     # permutation importance on its held-out rows (models/forest.py _attach_perm)
     permutation: Optional[Dict[str, Any]] = None
+    # RandomForest*: the job's train_params["partial_dependence"] as service.partial_dependence_options
+    # resolved it -- a kept fit also computes one-way partial dependence on its training rows
+    # (models/forest.py _attach_pd)
+    partial_dependence: Optional[Dict[str, Any]] = None
 
 
 @dataclass

@@ -52,6 +52,8 @@ from .base import (Family, FitOutput, FitTask, ParamError, as_bool, as_float, as
 _CLS = "RandomForestClassifier"
 _REG = "RandomForestRegressor"
 PERM_SHARDED = "permutation_importance is not computed for row-sharded jobs (run with parallelism='task')"
+PD_SHARDED = "partial_dependence is not computed for row-sharded jobs (run with parallelism='task')"
+PD_BINNED = "partial_dependence is not computed for a table resident only in binned form (the grids need the float32 rows)"
 
 _DEFAULT = object()   # "parameter not given"
 
@@ -293,6 +295,11 @@ class ForestFamily(Family):
         with trace.range("forest_plan"):
             Xb = data.binned()
         sharded = getattr(data, "is_row_shard", False)
+        pd_off = PD_SHARDED if sharded else (PD_BINNED if getattr(data, "X", None) is None else None)
+        if pd_off:   # _attach_pd computes nothing on these tables
+            for t in tasks:
+                if t.partial_dependence and pd_off not in t.params["warnings"]:
+                    t.params["warnings"] = t.params["warnings"] + [pd_off]
         if sharded:
             # the row-sharded builder sums histograms (medians need every row) and keeps no node
             # bounds: the cluster runner sends such jobs task-parallel (parallel/runner.py
@@ -551,6 +558,7 @@ class ForestFamily(Family):
                     o.model = extract_forest(fb, int(toff[f]), int(toff[f + 1]), data, t)
                     self._attach_oob(data, Xb, fb, specs, o, int(toff[f]), int(toff[f + 1]), t, 0)
                     self._attach_perm(data, Xb, fb, o, int(toff[f]), int(toff[f + 1]), t, 0)
+                    self._attach_pd(data, Xb, fb, o, int(toff[f]), int(toff[f + 1]), t, 0)
                 outs.append(o)
                 for fo in (follow or {}).get(t.task_id, []):   # prefix fits: leader f's first m trees
                     m = int(fo.params["n_estimators"])
@@ -573,6 +581,7 @@ class ForestFamily(Family):
                         of.model = extract_forest(fb, int(toff[f]), int(toff[f]) + m, data, fo, depth_cap=cap)
                         self._attach_oob(data, Xb, fb, specs, of, int(toff[f]), int(toff[f]) + m, fo, cap)
                         self._attach_perm(data, Xb, fb, of, int(toff[f]), int(toff[f]) + m, fo, cap)
+                        self._attach_pd(data, Xb, fb, of, int(toff[f]), int(toff[f]) + m, fo, cap)
                     outs.append(of)
             return outs
         finally:   # the node pool is an arena slot: free it for the next batch
@@ -626,6 +635,67 @@ class ForestFamily(Family):
         m["permutation_rows"] = (rows.cpu().numpy() if isinstance(rows, torch.Tensor) else np.asarray(rows)).astype(np.int32)
         m["permutation_meta"] = {"scoring": pi["scoring"], "n_repeats": int(opts["n_repeats"]),
                                  "random_state": int(opts["random_state"])}
+
+    def _attach_pd(self, data, Xb, fb, out: FitOutput, t0: int, t1: int, task: FitTask, cap: int) -> None:
+        """``FitTask.partial_dependence`` on a kept fit: sklearn's one-way brute-force partial
+        dependence (kind="average") of pool trees [t0, t1) over the fit's training rows
+        (docs/PARTIAL_DEPENDENCE.md): the grids are built on the host from the float32 columns,
+        binned with the table's edges, and forest_ops.partial_dependence_values walks every
+        feature and grid point in one fused pass.  A fit without the option launches and
+        allocates nothing."""
+        opts = task.partial_dependence
+        if not opts or getattr(data, "is_row_shard", False) or getattr(data, "X", None) is None:   # run() warned
+            return
+        rows = data.train_rows[task.split]
+        n_train = int(rows.numel())
+        if n_train == 0:
+            return
+        if opts["max_rows"] is not None and n_train > opts["max_rows"]:
+            pick = np.sort(np.random.RandomState(opts["random_state"]).choice(n_train, opts["max_rows"], replace=False))
+            rows = rows[torch.from_numpy(pick).to(rows.device)]
+        d = int(Xb.shape[1])
+        notes = []
+        want = list(range(d)) if opts["features"] is None else [int(f) for f in opts["features"]]
+        for f in want:
+            if not 0 <= f < d:
+                notes.append(f"partial_dependence: feature {f} is outside the table's {d} columns")
+        want = [f for f in want if 0 <= f < d]
+        Xs = data.X.index_select(0, rows.long())[:, want].t().contiguous().cpu().numpy() if want else None
+        edges = data.edges.cpu().numpy()
+        feats, grids, bins = [], [], []
+        for j, f in enumerate(want):
+            grid = forest_ops.partial_dependence_grid(Xs[j], opts["grid_resolution"], opts["percentiles"])
+            if grid is None:
+                notes.append(f"partial_dependence: feature {f}: percentiles are too close to each other")
+                continue
+            feats.append(f)
+            grids.append(grid)
+            bins.append(forest_ops.partial_dependence_bins(grid, edges[f]))
+        if notes:
+            out.info["warnings"] = list(out.info.get("warnings", [])) + notes
+        m = out.model
+        NT = 1 if (fb.is_reg or int(fb.n_classes) == 2) else int(fb.n_classes)
+        off = np.zeros(len(feats) + 1, dtype=np.int64)
+        np.cumsum([len(g) for g in grids], out=off[1:])
+        avg = np.zeros((NT, int(off[-1])), dtype=np.float64)
+        if feats:
+            sub = np.zeros((len(feats), max(len(b) for b in bins)), dtype=np.uint8)
+            for j, b in enumerate(bins):
+                sub[j, :len(b)] = b
+            on = fb.on_gpu
+            res = forest_ops.partial_dependence_values(fb, Xb if on else Xb.numpy(), t0, t1, rows if on else rows.numpy(),
+                                                       feats, sub, [len(b) for b in bins], depth_cap=cap)
+            for j in range(len(feats)):
+                avg[:, off[j]:off[j + 1]] = res["average"][j, :len(bins[j])].T
+        m["pd_features"] = np.asarray(feats, dtype=np.int32)
+        m["pd_grid_off"] = off
+        m["pd_grid_values"] = np.concatenate(grids) if grids else np.zeros(0, dtype=np.float64)
+        m["pd_average"] = avg
+        m["pd_rows"] = rows.cpu().numpy().astype(np.int32)
+        m["pd_meta"] = {"grid_resolution": int(opts["grid_resolution"]), "percentiles": [float(p) for p in opts["percentiles"]],
+                        "max_rows": opts["max_rows"], "random_state": int(opts["random_state"]),
+                        "features": None if opts["features"] is None else [int(f) for f in opts["features"]],
+                        "warnings": notes}
 
 
 def _early_ok(data, batch: List[FitTask], is_reg: bool, mono) -> bool:

@@ -1119,6 +1119,169 @@ def permutation_importance(scores: dict, scoring: Optional[str] = None) -> dict:
             "importances_std": imp.std(1), "scoring": name}
 
 
+def partial_dependence_grid(Xcol_rows, grid_resolution: int = 100, percentiles=(0.05, 0.95)) -> Optional[np.ndarray]:
+    """The grid of ``sklearn.inspection.partial_dependence`` (1.7 ``_grid_from_X``) for one float32
+    column restricted to the rows used, with the same calls so the values are equal: the column's
+    unique values when there are fewer than ``grid_resolution``, else ``grid_resolution`` points
+    evenly spaced between its two ``mquantiles``.  Float64 [G]; None when the two percentiles are
+    too close to each other (sklearn raises: the caller leaves the feature out)."""
+    from scipy.stats.mstats import mquantiles
+
+    col = np.asarray(Xcol_rows).reshape(-1)
+    uniques = np.unique(col)
+    if uniques.shape[0] < grid_resolution:
+        return uniques.astype(np.float64)
+    q = mquantiles(col, prob=tuple(percentiles), axis=0)
+    if np.allclose(q[0], q[1]):
+        return None
+    return np.linspace(q[0], q[1], num=int(grid_resolution), endpoint=True).astype(np.float64)
+
+
+def partial_dependence_bins(grid: np.ndarray, edges_row) -> np.ndarray:
+    """Bins of the grid values of one feature: ``bin(float32(v))`` by that feature's 255 edges, the
+    rule every table row is binned with (``dml_cpu_bin``).  uint8 [G]."""
+    g = np.ascontiguousarray(np.asarray(grid, dtype=np.float64).astype(np.float32).reshape(-1, 1))
+    e = edges_row.cpu().numpy() if isinstance(edges_row, torch.Tensor) else np.asarray(edges_row)
+    e = np.ascontiguousarray(e, dtype=np.float32).reshape(-1)
+    out = np.empty((g.shape[0], 1), dtype=np.uint8)
+    native.cpu_lib().dml_cpu_bin(native.ptr(g), g.shape[0], 1, native.ptr(e), native.ptr(out), 1)
+    return out.reshape(-1)
+
+
+# The kernel's per-block partials [blocks, features of one launch, G, n_targets] (float64) stay
+# under this many bytes: dml_forest_pd launches the features in chunks of PdArgs.f_chunk.
+PD_PART_BYTES = 64 << 20
+
+
+def _pred_group(is_reg: bool, n_classes: int) -> int:
+    """Trees dml_forest_pd walks in lock-step (predict.hip DML_PRED_U: 8, or 4 / 16; more than 32
+    classes never run 16 wide): the host twin groups the trees alike, so it skips the same walks."""
+    u = os.environ.get("DML_PRED_U", "")
+    if u == "16" and not is_reg and n_classes > 32:
+        return 8
+    return int(u) if u in ("4", "16") else 8
+
+
+def partial_dependence_values(fb: ForestBuild, Xb, t0: int, t1: int, rows, features, sub_bins, n_grid,
+                              depth_cap: int = 0, want_rows: bool = False, want_walked: bool = False,
+                              no_skip: bool = False) -> dict:
+    """One-way partial dependence of pool trees [t0, t1) over ``rows`` (dataset row ids): for
+    ``features[j]`` and each of its first ``n_grid[j]`` bins ``sub_bins[j]`` (uint8 [F, Gmax]),
+    every row is predicted from its own bins except that the feature's bin is the given one, and
+    the float32 values -- ``predict``'s, bit for bit: the class fractions ``proba`` (the positive
+    class alone for two classes) or the regression mean -- are averaged over the rows in float64.
+    GPU pool: predict.hip ``k_pd_cls`` / ``k_pd_reg`` / ``k_pd_reduce``; host pool: the twin,
+    csrc/runtime/forest_pd_cpu.cpp, which adds in the same order.  A bin that occurs twice in a
+    feature's list is walked once; a feature no node of the trees splits on is not walked: its
+    averages are the baseline's.  Returns
+
+    * ``average``: float64 [F, Gmax, n_targets] on the host (entries past ``n_grid[j]`` are NaN) and
+      ``baseline`` [n_targets], the mean of the unchanged rows;
+    * ``features``: the walked feature ids, in the order given; ``n``: the number of rows;
+    * with ``want_rows`` the per-row values ``rows`` float32 [F, Gmax, n, n_targets] and
+      ``base_rows`` [n, n_targets] on the pool's device; with ``want_walked`` the number of
+      (row, tree, distinct bin) slots per feature [F] that were walked a second time."""
+    is_reg, C = bool(fb.is_reg), int(fb.n_classes)
+    d = int(Xb.shape[1])
+    if not 0 <= t0 < t1 <= int(fb.n_trees):
+        raise ValueError(f"partial_dependence_values: trees [{t0}, {t1}) outside the pool's {fb.n_trees} trees")
+    rows_np = np.ascontiguousarray(rows.cpu().numpy() if isinstance(rows, torch.Tensor) else rows, dtype=np.int32)
+    n = len(rows_np)
+    if n == 0:
+        raise ValueError("partial_dependence_values: no rows")
+    if rows_np.min() < 0 or rows_np.max() >= int(Xb.shape[0]):
+        raise ValueError("partial_dependence_values: a row index is out of range")
+    feats_req = np.ascontiguousarray(features, dtype=np.int32).reshape(-1)
+    Fq = len(feats_req)
+    if Fq and (feats_req.min() < 0 or feats_req.max() >= d or len(np.unique(feats_req)) != Fq):
+        raise ValueError(f"partial_dependence_values: features must be distinct column positions in [0, {d})")
+    sub_np = np.asarray(sub_bins)
+    ng_np = np.asarray(n_grid, dtype=np.int64).reshape(-1)
+    if sub_np.ndim != 2 or sub_np.shape[0] != Fq or len(ng_np) != Fq:
+        raise ValueError("partial_dependence_values: sub_bins must be [len(features), Gmax] and n_grid [len(features)]")
+    Gq = int(sub_np.shape[1])
+    if Fq and (ng_np.min() < 1 or ng_np.max() > Gq):
+        raise ValueError("partial_dependence_values: n_grid must lie in [1, Gmax]")
+    if Fq and (sub_np.min() < 0 or sub_np.max() > 255):
+        raise ValueError("partial_dependence_values: a bin is outside [0, 255]")
+    NT, c0 = (1, 0) if is_reg else ((1, 1) if C == 2 else (C, 0))
+    used = set(used_features(fb, t0, t1, d, depth_cap).tolist())
+    # the walked slots: slot 0 is the baseline (-1), then the requested features some node splits
+    # on, each with its distinct bins (ascending)
+    walk = [j for j in range(Fq) if int(feats_req[j]) in used]
+    uniq = [np.unique(sub_np[j, :ng_np[j]].astype(np.uint8), return_inverse=True) for j in walk]
+    F = 1 + len(walk)
+    Gmax = max([1] + [len(u) for u, _ in uniq])
+    feats = np.array([-1] + [int(feats_req[j]) for j in walk], dtype=np.int32)
+    subs = np.zeros((F, Gmax), dtype=np.uint8)
+    ngs = np.ones(F, dtype=np.int32)
+    for s, (u, _inv) in enumerate(uniq, start=1):
+        subs[s, :len(u)], ngs[s] = u, len(u)
+    blocks = (n + 255) // 256
+    f_chunk = int(min(F, 65535, max(1, PD_PART_BYTES // (blocks * Gmax * NT * 8))))
+    if fb.on_gpu:
+        dev = fb.nodes.device
+        rows_t = (rows if isinstance(rows, torch.Tensor) else torch.from_numpy(rows_np)).to(dev, torch.int32).contiguous()
+        feats_t, subs_t, ngs_t = (torch.from_numpy(a).to(dev) for a in (feats, subs, ngs))
+        toff = torch.tensor([t0, t1], dtype=torch.int32).to(dev)
+        roff = torch.tensor([0, n], dtype=torch.int64).to(dev)
+        part = torch.empty((blocks, f_chunk, Gmax, NT), dtype=torch.float64, device=dev)
+        out = torch.zeros((F, Gmax, NT), dtype=torch.float64, device=dev)
+        vrows = torch.zeros((F, Gmax, n, NT), dtype=torch.float32, device=dev) if want_rows else None
+        walked = torch.zeros(F, dtype=torch.int64, device=dev) if want_walked else None
+        top = torch.empty((int(t1) * TOP_SLOTS_MAX, 2), dtype=torch.int32, device=dev)   # indexed by pool tree id
+        o = native.PdArgs()
+        o.Xb, o.ld, o.d = native.ptr(Xb), Xb.stride(0), d
+        o.nodes, o.node_val, o.VC = native.ptr(fb.nodes), native.ptr(fb.vals), int(fb.VC)
+        o.is_reg, o.n_classes = int(is_reg), C
+        o.fit_tree_off, o.fit_row_off, o.t0, o.t1 = native.ptr(toff), native.ptr(roff), int(t0), int(t1)
+        o.rows, o.n_rows, o.depth_cap = native.ptr(rows_t), n, int(depth_cap)
+        o.features, o.F, o.sub_bins, o.Gmax, o.n_grid = native.ptr(feats_t), F, native.ptr(subs_t), Gmax, native.ptr(ngs_t)
+        o.n_targets, o.c0, o.part, o.f_chunk = NT, c0, native.ptr(part), f_chunk
+        o.out, o.out_rows, o.out_walked = native.ptr(out), native.ptr(vrows), native.ptr(walked)
+        o.toptab, o.no_skip = native.ptr(top), int(no_skip)
+        with trace.range("forest_pd"):
+            rc = native.hip_lib().dml_forest_pd(ctypes.byref(o), native.stream_handle(dev))
+        if rc:
+            raise RuntimeError(f"dml_forest_pd failed ({rc})")
+        torch.cuda.current_stream(dev).synchronize()   # keep the scratch and index arrays alive until done
+        sums = out.cpu().numpy()
+        walked_np = walked.cpu().numpy() if want_walked else None
+    else:
+        dev = torch.device("cpu")
+        Xb_np = np.ascontiguousarray(Xb.numpy() if isinstance(Xb, torch.Tensor) else Xb)
+        nodes = np.ascontiguousarray(fb.nodes, dtype=np.int32)
+        vals = np.ascontiguousarray(fb.vals, dtype=np.float64)
+        part_np = np.empty((blocks, F, Gmax, NT), dtype=np.float64)
+        sums = np.zeros((F, Gmax, NT), dtype=np.float64)
+        vrows_np = np.zeros((F, Gmax, n, NT), dtype=np.float32) if want_rows else None
+        walked_u = np.zeros(F, dtype=np.uint64) if want_walked else None
+        native.cpu_lib().dml_cpu_forest_pd(
+            native.ptr(Xb_np), Xb_np.shape[1], native.ptr(nodes), native.ptr(vals), int(fb.VC), int(is_reg), C,
+            int(t0), int(t1), native.ptr(rows_np), n, int(depth_cap), native.ptr(feats), F, native.ptr(subs), Gmax,
+            native.ptr(ngs), NT, c0, _pred_group(is_reg, C), int(no_skip), native.ptr(part_np), native.ptr(sums),
+            native.ptr(vrows_np), native.ptr(walked_u))
+        vrows = torch.from_numpy(vrows_np) if want_rows else None
+        walked_np = walked_u.astype(np.int64) if want_walked else None
+    mean = sums / float(n)
+    average = np.full((Fq, Gq, NT), np.nan, dtype=np.float64)
+    for j in range(Fq):
+        average[j, :ng_np[j]] = mean[0, 0]           # unwalked features: the baseline's mean
+    for s, (j, (_u, inv)) in enumerate(zip(walk, uniq), start=1):
+        average[j, :ng_np[j]] = mean[s, inv.reshape(-1)]
+    res = {"average": average, "baseline": mean[0, 0].copy(), "features": feats[1:].copy(), "n": n, "is_reg": is_reg}
+    if want_rows:
+        full = vrows[0, :1].expand(Fq, Gq, n, NT).clone()
+        for s, (j, (_u, inv)) in enumerate(zip(walk, uniq), start=1):
+            full[j, :ng_np[j]] = vrows[s, torch.from_numpy(inv.reshape(-1).astype(np.int64)).to(dev)]
+        res["rows"], res["base_rows"] = full, vrows[0, 0].clone()
+    if want_walked:
+        w = np.zeros(Fq, dtype=np.int64)
+        w[walk] = walked_np[1:]
+        res["walked"], res["base_walked"] = w, int(walked_np[0])
+    return res
+
+
 def feature_importances(nodes, vals, n_trees: int, d: int, is_reg: bool, criterion: int) -> np.ndarray:
     """sklearn's ``feature_importances_`` (mean decrease in impurity) of trees rooted at nodes
     0 .. n_trees-1 of a pool: float64 [d].

@@ -64,7 +64,7 @@ import torch
 
 from ..engine import faults
 from ..engine.jobs import Job, json_safe
-from ..engine.service import (Controller, Runner, attach_model, attach_permutation, candidate_costs, job_plan,
+from ..engine.service import (Controller, Runner, attach_entry, attach_model, attach_permutation, candidate_costs, job_plan,
                               job_seed, pick_refit, plan_slices, presize_for_job, publish_results, refit_model,
                               refit_with_permutation, run_slice, should_recut)
 from ..models.base import family_of, is_classifier
@@ -561,6 +561,11 @@ class WorkerCore:
         out = {"model_path": path, "wall": time.perf_counter() - t0}
         if entry is not None:   # train_params["permutation_importance"]: the winner's holdout importances
             out["permutation_importance"] = entry
+        from ..engine.executor import partial_dependence_entry
+
+        pd_entry = partial_dependence_entry(model)
+        if pd_entry is not None:   # train_params["partial_dependence"]: the refit model's own curves
+            out["partial_dependence"] = pd_entry
         return out
 
 
@@ -1527,6 +1532,9 @@ class DistributedRunner(Runner):
             if out.get("permutation_importance") and js.refit_candidate >= 0:
                 attach_permutation(self.ctl, js.job, js.done.get(js.held, []), js.refit_candidate,
                                    out["permutation_importance"])
+            if out.get("partial_dependence") and js.refit_candidate >= 0:
+                attach_entry(self.ctl, js.job, js.done.get(js.held, []), js.refit_candidate, "partial_dependence",
+                             out["partial_dependence"])
             self._finish_job(js, out.get("model_path"))
             return
         # slice

@@ -103,6 +103,14 @@ PermArgs = _i64_struct(
      "out_walked", "toptab", "no_skip"],
 )
 
+# csrc/kernels/predict.hip PdArgs (partial-dependence sums of one kept fit)
+PdArgs = _i64_struct(
+    "PdArgs",
+    ["Xb", "ld", "d", "nodes", "node_val", "VC", "is_reg", "n_classes", "fit_tree_off", "fit_row_off", "t0", "t1",
+     "rows", "n_rows", "depth_cap", "features", "F", "sub_bins", "Gmax", "n_grid", "n_targets", "c0", "part",
+     "f_chunk", "out", "out_rows", "out_walked", "toptab", "no_skip"],
+)
+
 # csrc/kernels/lr_mfma.hip argument blocks (MFMA logistic-regression objective)
 LrFwdArgs = _i64_struct(
     "LrFwdArgs",
@@ -166,6 +174,9 @@ def cpu_lib() -> ctypes.CDLL:
             lib.dml_boot_weight_oob.argtypes = [c_vp, ctypes.c_uint32, c_vp]
             lib.dml_cpu_forest_perm.argtypes = [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_i64,
                                                 c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]
+            lib.dml_cpu_forest_pd.argtypes = [c_vp, c_i64, c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_vp, c_i64,
+                                              c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp,
+                                              c_vp, c_vp, c_vp]
             lib.dml_cpu_bin.argtypes = [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64]
             lib.dml_cpu_svm_sizeof_prob.restype = c_i32
             lib.dml_cpu_svm_smo.argtypes = [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]
@@ -224,6 +235,11 @@ def hip_lib() -> ctypes.CDLL:
                 raise RuntimeError("PermArgs layout mismatch between HIP library and Python")
             lib.dml_forest_perm.restype = c_i32
             lib.dml_forest_perm.argtypes = [ctypes.POINTER(PermArgs), c_vp]
+            lib.dml_pd_sizeof_args.restype = c_i32
+            if lib.dml_pd_sizeof_args() != ctypes.sizeof(PdArgs):
+                raise RuntimeError("PdArgs layout mismatch between HIP library and Python")
+            lib.dml_forest_pd.restype = c_i32
+            lib.dml_forest_pd.argtypes = [ctypes.POINTER(PdArgs), c_vp]
             lib.dml_bin.restype = c_i32
             lib.dml_bin.argtypes = [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp]
             _register_optional(lib)
