@@ -24,6 +24,12 @@
 //                  8-pass radix select on order-preserving 64-bit keys of the float64 values
 //                  (one histogram pass + one pick pass per byte), no sort
 //
+//   k_gb_stage_stats / k_gb_stage_stats_reduce
+//                  after a stage, every recorded (fit, row): the loss term and the score statistic
+//                  from the updated raw scores, summed per fit over its in-bag, out-of-bag and
+//                  held-out rows in a fixed order (train_score_, oob_scores_, the staged CV score;
+//                  docs/GBRT_STAGED.md)
+//
 // A leaf is addressed by its PATH SLOT: 1 at the root, 2 s + (went right) per level, so a
 // tree of depth <= D has slots in [1, 2^(D+1)) and per-tree leaf arrays need no node index.
 // Depths up to 10 (S = 2048: 56 KB of leaf-sum LDS per workgroup, uint16 slot ids).
@@ -500,6 +506,185 @@ __global__ __launch_bounds__(256) void k_exp_hist(const float* __restrict__ y, i
   if (threadIdx.x == 0 && nb) atomicAdd(bad, (unsigned long long)nb);
 }
 
+// ---- per-stage loss / score statistics ------------------------------------------------
+// After a stage's raw update: for every recorded fit, the loss sum and the score statistic of
+// its in-bag (0), out-of-bag (1) and held-out (2) rows -- sklearn's train_score_ / oob_scores_
+// and the staged CV score, all from the raw scores the stage has just written.  One launch for
+// all fits (grid.y), nothing read back until the stage loop ends (models/boosting.py).
+struct GbStatsArgs {
+  int64_t n, K, A;            // rows, classes per fit (1: binary / regression), fits of this launch
+  int64_t raw;                // double [F * K][n]
+  int64_t ycls;               // int32 [n] class ids (classification losses)
+  int64_t yreg;               // double [n] (regression losses)
+  int64_t roles;              // uint8 [n_splits][n]: search/cv.py ROLE_* of every split
+  int64_t inbag;              // uint8 [rows][n]: the stage's in-bag masks
+  int64_t val;                // uint8 [rows][n] early-stopping validation masks (0: none)
+  int64_t fit_raw;            // int32 [A]: first raw row of the fit (fit * K)
+  int64_t fit_loss;           // int32 [A] (GbLoss)
+  int64_t fit_role;           // int32 [A]: the fit's row of `roles`
+  int64_t fit_inbag;          // int32 [A]: the fit's row of `inbag`
+  int64_t fit_val;            // int32 [A]: the fit's row of `val` (-1: no validation rows)
+  int64_t fit_out;            // int32 [A]: the fit's slot in `stats`
+  int64_t fit_dpos;           // int32 [A]: the fit's entry of `delta`
+  int64_t fit_alpha;          // double [A]: quantile alpha
+  int64_t delta;              // double []: huber delta of this stage (0 pointer: 0.0)
+  int64_t part;               // 8-byte words [blocks][A][3][3] scratch, then the reduction's levels
+  int64_t stats;              // 8-byte words [fits][n_stages][3][3]: per category {n int64,
+                              //   match count int64 (classification) | SSE double, loss sum double}
+  int64_t stage, n_stages;    // destination stage index, stages per fit in `stats`
+};
+
+constexpr int kStatsRegK = 8;   // classes held in registers; above: the row's values are read twice
+
+// xor-shuffle sum over the 64 lanes (every lane ends with the wave's sum), offsets 32 .. 1
+__device__ __forceinline__ double gb_wave_sum(double s) {
+  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+  return s;
+}
+
+// the loss term and score statistic of one row: sklearn 1.7 _loss half-losses (link space)
+__device__ __forceinline__ void gb_row_terms_reg(int loss, double x, double y, double alpha, double delta, double* term,
+                                                 double* se) {
+#pragma clang fp contract(off)
+  const double e = x - y;
+  *se = e * e;
+  const double d = y - x;
+  const double ad = fabs(d);
+  double t;
+  if (loss == kGbSq) t = 0.5 * d * d;
+  else if (loss == kGbAbs) t = ad;
+  else if (loss == kGbQuant) t = d >= 0.0 ? alpha * d : (alpha - 1.0) * d;
+  else t = ad <= delta ? 0.5 * d * d : delta * (ad - 0.5 * delta);
+  *term = t;
+}
+
+// KREG > 0: a fit's K <= KREG class values stay in registers (fully unrolled, no indexed
+// access); KREG == 0: any K, the values are read once for the maximum and once for the sum
+template <int KREG>
+__global__ __launch_bounds__(256) void k_gb_stage_stats(GbStatsArgs a) {
+  __shared__ double red_d[4][6];
+  __shared__ long long red_i[4][6];
+  const int fa = blockIdx.y;
+  const int64_t n = a.n;
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int K = (int)a.K;
+  const int loss = GB_PTR(const int32_t, a.fit_loss)[fa];
+  const bool is_cls = loss == kGbLog || loss == kGbExp;
+  int cat = -1;
+  if (r < n) {
+    const uint8_t role = GB_PTR(const uint8_t, a.roles)[(int64_t)GB_PTR(const int32_t, a.fit_role)[fa] * n + r];
+    const int vrow = a.val ? GB_PTR(const int32_t, a.fit_val)[fa] : -1;
+    const bool isval = vrow >= 0 && GB_PTR(const uint8_t, a.val)[(int64_t)vrow * n + r] != 0;
+    if (role == 2) cat = 2;
+    else if (role == 1 && !isval)
+      cat = GB_PTR(const uint8_t, a.inbag)[(int64_t)GB_PTR(const int32_t, a.fit_inbag)[fa] * n + r] ? 0 : 1;
+  }
+  double term = 0.0, se = 0.0;
+  bool match = false;
+  if (cat >= 0) {
+    const double* raw = GB_PTR(const double, a.raw) + (int64_t)GB_PTR(const int32_t, a.fit_raw)[fa] * n + r;
+    if (!is_cls) {
+      const double delta = a.delta ? GB_PTR(const double, a.delta)[GB_PTR(const int32_t, a.fit_dpos)[fa]] : 0.0;
+      gb_row_terms_reg(loss, raw[0], GB_PTR(const double, a.yreg)[r], GB_PTR(const double, a.fit_alpha)[fa], delta,
+                       &term, &se);
+    } else {
+      const int y = GB_PTR(const int32_t, a.ycls)[r];
+      if (K == 1) {
+        const double z = raw[0];
+        match = (z >= 0.0 ? 1 : 0) == y;
+        if (loss == kGbExp) term = exp(y ? -z : z);
+        else term = fmax(z, 0.0) + log1p(exp(-fabs(z))) - (y ? z : 0.0);
+      } else {
+        double mx = -INFINITY, ry = 0.0, s = 0.0;
+        int arg = 0;
+        if (KREG > 0) {
+          double v[KREG > 0 ? KREG : 1];
+#pragma unroll
+          for (int k = 0; k < KREG; ++k) {
+            v[k] = k < K ? raw[(int64_t)k * n] : -INFINITY;
+            if (v[k] > mx) { mx = v[k]; arg = k; }   // strict: the first maximum
+            if (k == y) ry = v[k];
+          }
+#pragma unroll
+          for (int k = 0; k < KREG; ++k)
+            if (k < K) s += exp(v[k] - mx);
+        } else {
+          for (int k = 0; k < K; ++k) {
+            const double v = raw[(int64_t)k * n];
+            if (v > mx) { mx = v; arg = k; }
+            if (k == y) ry = v;
+          }
+          for (int k = 0; k < K; ++k) s += exp(raw[(int64_t)k * n] - mx);
+        }
+        match = arg == y;
+        term = (mx + log(s)) - ry;
+      }
+    }
+  }
+  // block sums in a fixed order: lanes by xor-shuffle, then the four waves ascending; the counts
+  // are integers (ballots), exact in any order
+  const int w = threadIdx.x >> 6;
+  const bool lane0 = (threadIdx.x & 63) == 0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const bool in = cat == c;
+    const long long cnt = __popcll(__ballot(in));
+    const long long hit = __popcll(__ballot(in && match));
+    const double ls = gb_wave_sum(in ? term : 0.0);
+    const double ss = is_cls ? 0.0 : gb_wave_sum(in ? se : 0.0);   // block-uniform branch
+    if (lane0) { red_i[w][2 * c] = cnt; red_i[w][2 * c + 1] = hit; red_d[w][2 * c] = ss; red_d[w][2 * c + 1] = ls; }
+  }
+  __syncthreads();
+  if (threadIdx.x < 9) {
+    const int c = threadIdx.x / 3, q = threadIdx.x % 3;
+    unsigned long long* out = GB_PTR(unsigned long long, a.part) + (((int64_t)blockIdx.x * a.A + fa) * 3 + c) * 3 + q;
+    if (q == 0 || (q == 1 && is_cls)) {
+      const int i = q == 0 ? 2 * c : 2 * c + 1;
+      *out = (unsigned long long)(red_i[0][i] + red_i[1][i] + red_i[2][i] + red_i[3][i]);
+    } else {
+      const int i = q == 1 ? 2 * c : 2 * c + 1;
+      *out = (unsigned long long)__double_as_longlong(red_d[0][i] + red_d[1][i] + red_d[2][i] + red_d[3][i]);
+    }
+  }
+}
+
+// One level of the reduction: out[g][j] = in[16 g][j] + .. + in[16 g + 15][j] in that order, one
+// thread per (group, entry); a group's 16 loads are issued together.  The host runs levels until
+// one group is left, whose sums go to stats[fit][stage][c][q] (out == nullptr).  A fixed order,
+// no floating-point atomics: the same sum every run, and the host twin's.  (One thread per entry
+// adding all ceil(n / 256) block partials in turn, as predict.hip k_perm_reduce does for its few
+// hundred blocks, took 2.0 ms for the 3,907 blocks of a 1M-row table: one dependent L2 load per
+// block.)
+constexpr int kStatsFan = 16;
+__global__ __launch_bounds__(256) void k_gb_stage_stats_reduce(GbStatsArgs a, const unsigned long long* __restrict__ in,
+                                                               int64_t n_in, unsigned long long* __restrict__ out) {
+  const int64_t j = (int64_t)blockIdx.y * 256 + threadIdx.x, E = a.A * 9;
+  if (j >= E) return;
+  const int64_t g = blockIdx.x, b0 = g * kStatsFan;
+  const int live = (int)(n_in - b0 < kStatsFan ? n_in - b0 : kStatsFan);
+  const int fa = (int)(j / 9), q = (int)(j % 3);
+  const int loss = GB_PTR(const int32_t, a.fit_loss)[fa];
+  const bool as_int = q == 0 || (q == 1 && (loss == kGbLog || loss == kGbExp));
+  unsigned long long v[kStatsFan];
+#pragma unroll
+  for (int i = 0; i < kStatsFan; ++i) v[i] = i < live ? in[(b0 + i) * E + j] : 0ull;
+  unsigned long long res;
+  if (as_int) {
+    long long acc = 0;
+#pragma unroll
+    for (int i = 0; i < kStatsFan; ++i) acc += (long long)v[i];
+    res = (unsigned long long)acc;
+  } else {
+    double acc = 0.0;
+#pragma unroll
+    for (int i = 0; i < kStatsFan; ++i)
+      if (i < live) acc += __longlong_as_double((long long)v[i]);
+    res = (unsigned long long)__double_as_longlong(acc);
+  }
+  if (out) out[g * E + j] = res;
+  else GB_PTR(unsigned long long, a.stats)[((int64_t)GB_PTR(const int32_t, a.fit_out)[fa] * a.n_stages + a.stage) * 9 + j % 9] = res;
+}
+
 // the 8 byte passes of the (tree, leaf) percentile select (state zeroed, hist zero on entry)
 template <int SV>
 int leaf_select(GbStageArgs* a, dim3 grid, hipStream_t st) {
@@ -652,6 +837,38 @@ int dml_gb_fit_sel_step(GbGradArgs* a, int which, int shift, hipStream_t st) {
     k_sel_delta<<<(unsigned)((a->A + 255) / 256), 256, 0, st>>>(*a);
   } else {
     return 2;
+  }
+  return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int dml_gb_sizeof_stats_args() { return (int)sizeof(GbStatsArgs); }
+
+// loss / score statistics of A fits over their in-bag, out-of-bag and held-out rows into
+// stats[fit_out[a]][stage] (k_gb_stage_stats, then k_gb_stage_stats_reduce level by level); part
+// holds A * 9 words per block and per group of every level but the last (ops/gbrt_ops.py
+// part_words)
+int dml_gb_stage_stats(GbStatsArgs* a, hipStream_t st) {
+  if (a->A <= 0 || a->n <= 0) return 0;
+  if (a->A > 65535 || a->K < 1 || a->stage < 0 || a->stage >= a->n_stages) return 2;
+  if (!a->raw || !a->roles || !a->inbag || !a->part || !a->stats || !a->fit_raw || !a->fit_loss || !a->fit_role ||
+      !a->fit_inbag || !a->fit_out || !a->fit_alpha || !a->fit_dpos || (a->val && !a->fit_val))
+    return 2;
+  const int64_t blocks = (a->n + 255) / 256;
+  const dim3 grid((unsigned)blocks, (unsigned)a->A);
+  if (a->K <= kStatsRegK) k_gb_stage_stats<kStatsRegK><<<grid, 256, 0, st>>>(*a);
+  else k_gb_stage_stats<0><<<grid, 256, 0, st>>>(*a);
+  // the block partials, then each level's group sums behind them, 16 to 1 until one group is left
+  const int64_t E = a->A * 9;
+  const unsigned long long* in = (const unsigned long long*)(uintptr_t)a->part;
+  unsigned long long* next = (unsigned long long*)(uintptr_t)a->part + blocks * E;
+  for (int64_t n_in = blocks;;) {
+    const int64_t groups = (n_in + kStatsFan - 1) / kStatsFan;
+    const dim3 rgrid((unsigned)groups, (unsigned)((E + 255) / 256));
+    k_gb_stage_stats_reduce<<<rgrid, 256, 0, st>>>(*a, in, n_in, groups == 1 ? nullptr : next);
+    if (groups == 1) break;
+    in = next;
+    next += groups * E;
+    n_in = groups;
   }
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }

@@ -56,6 +56,10 @@ class JobSpec:
     # refit computes it (service.refit_model sets FitTask.partial_dependence); here it only names
     # the tables on which the refit will compute nothing
     partial_dependence: Optional[Dict[str, Any]] = None
+    # train_params["staged_scores"] as service.job_plan resolved it (GradientBoosting* only): every
+    # CV and holdout fit records its held-out score after every stage (FitTask.staged), and a
+    # candidate's result gains ``staged_scores`` (staged_entry)
+    staged: Optional[Dict[str, Any]] = None
 
     def split_key(self):
         return (self.cv, self.holdout, str(self.test_size), str(self.random_state), is_classifier(self.model_type))
@@ -185,6 +189,9 @@ def run_candidates(data, spec: JobSpec, candidate_ids: Sequence[int]) -> List[Ca
             t.keep = t.split == hold
             if perm_all and t.keep:
                 t.permutation = spec.permutation
+    if spec.staged:
+        for t in tasks:
+            t.staged = spec.staged
     outputs: Dict[int, FitOutput] = {}
     if tasks:
         try:
@@ -258,7 +265,8 @@ def run_candidates(data, spec: JobSpec, candidate_ids: Sequence[int]) -> List[Ca
                     R["mean_squared_error"] = -_scores_for(data, t, o, "neg_mean_squared_error")
                 R["training_time"] = o.fit_seconds
                 model = o.model
-                if isinstance(model, dict) and model.get("oob_score") is not None:   # RandomForest* oob_score=True
+                if isinstance(model, dict) and model.get("kind") == "forest" and \
+                        model.get("oob_score") is not None:   # RandomForest* oob_score=True
                     R["oob_score"] = float(model["oob_score"])
                     for w in o.info.get("warnings", []):   # the kept fit's own (rows no tree left out)
                         if w not in warnings:
@@ -291,6 +299,10 @@ def run_candidates(data, spec: JobSpec, candidate_ids: Sequence[int]) -> List[Ca
                 main = "score" if self_scored else ("accuracy" if clf else "r2_score")
                 R["cv_scores"] = []
                 R["mean_cv_score"] = R.get(main, float("nan"))
+            if spec.staged:
+                entry = staged_entry([split_out[s][1] for s in cv_idx], hold_out)
+                if entry is not None:
+                    R["staged_scores"] = entry
             R["scoring"] = scorer
             R["fit_time_total"] = fit_s
             its = [split_out[s][1].info.get("n_iter") for s in cv_idx if split_out[s][1] is not None]
@@ -320,6 +332,32 @@ def permutation_entry(model) -> Optional[Dict[str, Any]]:
             "baseline_score": float(model["permutation_baseline_score"]),
             "scoring": meta.get("scoring"), "n_repeats": meta.get("n_repeats"),
             "random_state": meta.get("random_state")}
+
+
+def staged_entry(cv_outs, hold_out) -> Optional[Dict[str, Any]]:
+    """The ``staged_scores`` entry of a J4 result from the fits' ``info["staged"]`` curves: the CV
+    score after every stage as plain lists.  Folds that early stopping ended at different stages
+    are cut to the shortest (``n_stages``); ``best_stage`` is 1-based, the first maximum of
+    ``mean_cv_score``.  None when no fit carries a curve (row-sharded jobs)."""
+    curves = [o.info["staged"] for o in cv_outs if o is not None and not o.error and o.info.get("staged")]
+    hold = hold_out.info.get("staged") if hold_out is not None and not hold_out.error else None
+    if not curves and hold is None:
+        return None
+    S = min(len(c["score"]) for c in curves + ([hold] if hold is not None else []))
+    entry: Dict[str, Any] = {"scoring": (curves[0] if curves else hold)["scoring"], "n_stages": int(S)}
+    if curves:
+        sc = np.asarray([c["score"][:S] for c in curves], dtype=np.float64)
+        entry["cv_scores"] = sc.tolist()
+        entry["mean_cv_score"] = sc.mean(0).tolist()
+        entry["std_cv_score"] = sc.std(0).tolist()
+        entry["mean_cv_loss"] = np.asarray([c["loss"][:S] for c in curves], dtype=np.float64).mean(0).tolist()
+        best = int(np.argmax(sc.mean(0))) if S else 0
+        entry["best_stage"] = best + 1
+        entry["best_stage_score"] = float(sc.mean(0)[best]) if S else float("nan")
+    if hold is not None:
+        entry["holdout_score"] = list(hold["score"][:S])
+        entry["holdout_loss"] = list(hold["loss"][:S])
+    return entry
 
 
 PD_MODEL_KEYS = ("pd_features", "pd_grid_off", "pd_grid_values", "pd_average", "pd_rows", "pd_meta")

@@ -31,7 +31,8 @@ _ARRAY_KEYS = ("nodes", "vals", "edges", "coef", "intercept", "X", "y", "init", 
                "components", "var", "min", "max", "value", "roots", "feature_importances", "oob_rows",
                "oob_decision_function", "oob_prediction", "permutation_importances", "permutation_importances_mean",
                "permutation_importances_std", "permutation_baseline_score", "permutation_rows", "pd_features",
-               "pd_grid_off", "pd_grid_values", "pd_average", "pd_rows")
+               "pd_grid_off", "pd_grid_values", "pd_average", "pd_rows", "train_score", "oob_scores", "oob_improvement",
+               "staged_test_score", "staged_test_loss")
 
 
 def save_model(model: Dict[str, Any], path: str) -> str:
@@ -295,6 +296,12 @@ class Predictor:
     def feature_importances_(self) -> np.ndarray:
         """Mean decrease in impurity (ops/forest_ops.py ``feature_importances``).  A forest
         artefact saved without the vector computes it from its nodes and node sums."""
+        if self.kind == "gbrt":   # sklearn's GradientBoosting rule, accumulated during the fit
+            fi = self.model.get("feature_importances")
+            if fi is None:
+                raise AttributeError(f"{self.model_type} artefact has no feature_importances_ (it was saved before "
+                                     f"gradient-boosting artefacts carried them, or by a row-sharded fit)")
+            return np.asarray(fi, dtype=np.float64)
         if self.kind != "forest":
             raise AttributeError(f"{self.model_type} artefact has no feature_importances_")
         fi = self.model.get("feature_importances")
@@ -322,7 +329,71 @@ class Predictor:
 
     @property
     def oob_score_(self) -> float:
+        """Forests: the out-of-bag score.  GradientBoosting: the last ``oob_scores_`` (a loss)."""
+        if self.kind == "gbrt":
+            return float(self._gbrt_stage("oob_score", "oob_score_", True))
         return float(self._oob("oob_score", "oob_score_"))
+
+    # ---- fitted gradient-boosting attributes (docs/GBRT_STAGED.md) ------------------------
+    def _gbrt_stage(self, key: str, name: str, oob: bool = False):
+        v = self.model.get(key) if self.kind == "gbrt" else None
+        if v is None:
+            why = "fit with subsample < 1" if oob and self.kind == "gbrt" else \
+                "a GradientBoosting artefact saved with its per-stage statistics"
+            raise AttributeError(f"{self.model_type} artefact has no {name} ({why})")
+        return v
+
+    @property
+    def n_estimators_(self) -> int:
+        """Stages actually fitted (early stopping may end before ``n_estimators``)."""
+        if self.kind != "gbrt":
+            raise AttributeError(f"{self.model_type} artefact has no n_estimators_")
+        return int(np.asarray(self.model["roots"]).shape[0])
+
+    @property
+    def train_score_(self) -> np.ndarray:
+        """sklearn's ``train_score_`` [n_estimators_]: the loss of the in-bag rows after every stage."""
+        return np.asarray(self._gbrt_stage("train_score", "train_score_"), dtype=np.float64)
+
+    @property
+    def oob_scores_(self) -> np.ndarray:
+        return np.asarray(self._gbrt_stage("oob_scores", "oob_scores_", True), dtype=np.float64)
+
+    @property
+    def oob_improvement_(self) -> np.ndarray:
+        return np.asarray(self._gbrt_stage("oob_improvement", "oob_improvement_", True), dtype=np.float64)
+
+    def staged_decision_function(self, X):
+        """sklearn's generator: the raw scores [n, k] after every stage (k = 1 for binary
+        classification and regression), on the host from the stage trees."""
+        if self.kind != "gbrt":
+            raise AttributeError(f"{self.model_type} artefact has no staged_decision_function")
+        from ..models.boosting import gbrt_staged_raw_numpy
+
+        return gbrt_staged_raw_numpy(self.model, X)
+
+    def staged_predict(self, X):
+        """sklearn's generator: the prediction after every stage, with ``predict``'s rule."""
+        def label(raw):
+            if self.classes_ is None:
+                return raw[:, 0]
+            return self.classes_[(raw[:, 0] >= 0).astype(int) if raw.shape[1] == 1 else raw.argmax(1)]
+
+        return (label(raw) for raw in self.staged_decision_function(X))
+
+    def staged_predict_proba(self, X):
+        """sklearn's generator: the class probabilities after every stage."""
+        if not self.is_classifier:
+            raise AttributeError(f"{self.model_type} is not a classifier")
+        from ..models.boosting import LOSS_EXP
+
+        def proba(raw):
+            if raw.shape[1] == 1:
+                p1 = _sigmoid(2.0 * raw[:, 0] if int(self.model["loss"]) == LOSS_EXP else raw[:, 0])
+                return np.stack([1.0 - p1, p1], 1)
+            return _softmax(raw)
+
+        return (proba(raw) for raw in self.staged_decision_function(X))
 
     @property
     def oob_decision_function_(self) -> np.ndarray:

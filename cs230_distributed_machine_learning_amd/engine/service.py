@@ -105,6 +105,37 @@ def permutation_options(tp: Dict[str, Any], model_type: str, holdout: bool, job_
     return {"n_repeats": int(k), "random_state": int(rs), "scoring": scoring, "candidates": cands}
 
 
+STAGED_KEYS = ("scoring",)
+
+
+def staged_options(tp: Dict[str, Any], model_type: str) -> Optional[Dict[str, Any]]:
+    """``train_params["staged_scores"]`` (True or a dict of ``STAGED_KEYS``) resolved to
+    {"scoring"}; None when the job does not ask.  ``scoring=None`` is accuracy / r2."""
+    from ..ops.forest_ops import PERM_SCORERS
+
+    v = tp.get("staged_scores")
+    if v is None or v is False:
+        return None
+    if v is True:
+        v = {}
+    if not isinstance(v, dict):
+        raise ParamError(f"train_params.staged_scores must be true or a dict of {', '.join(STAGED_KEYS)}")
+    unknown = sorted(k for k in v if k not in STAGED_KEYS)
+    if unknown:
+        raise ParamError(f"staged_scores: unknown key(s) {unknown}; supported: {list(STAGED_KEYS)}")
+    if model_type not in ("GradientBoostingClassifier", "GradientBoostingRegressor"):
+        raise ParamError(f"staged_scores is available for GradientBoostingClassifier and "
+                         f"GradientBoostingRegressor, not {model_type}")
+    is_reg = model_type == "GradientBoostingRegressor"
+    scoring = v.get("scoring")
+    if scoring in (None, "None", ""):
+        scoring = PERM_SCORERS[is_reg][0]
+    if scoring not in PERM_SCORERS[is_reg]:
+        raise ParamError(f"staged_scores: scoring {scoring!r} is not supported for {model_type}; "
+                         f"supported: {list(PERM_SCORERS[is_reg])}")
+    return {"scoring": scoring}
+
+
 PD_KEYS = ("features", "grid_resolution", "percentiles", "max_rows", "random_state")
 
 
@@ -184,6 +215,7 @@ def job_plan(request: Dict[str, Any]) -> Dict[str, Any]:
         raise ParamError(f"{model_type} has no row-sharded (data-parallel) fit; use parallelism 'task'")
     perm = permutation_options(tp, model_type, bool(tp.get("holdout", True)), request.get("job_id"))
     pd_opts = partial_dependence_options(tp, model_type)
+    staged = staged_options(tp, model_type)
     plan = {
         "model_type": model_type, "search_type": search_type, "candidates": cands, "cv": cv,
         "scoring": scoring, "error_score": error_score, "refit": bool(refit) if not isinstance(refit, str) else True,
@@ -200,6 +232,8 @@ def job_plan(request: Dict[str, Any]) -> Dict[str, Any]:
         plan["permutation_importance"] = perm
     if pd_opts is not None:
         plan["partial_dependence"] = pd_opts
+    if staged is not None:
+        plan["staged_scores"] = staged
     return plan
 
 
@@ -599,7 +633,7 @@ def run_slice(plan: Dict[str, Any], params: List[Dict[str, Any]], subtask_ids: L
                    holdout=plan["holdout"], test_size=plan["test_size"], random_state=plan["random_state"],
                    error_score=plan["error_score"], keep_models="all" if keep_all else "none", seed=seed,
                    raise_batch_errors=True, permutation=plan.get("permutation_importance"),
-                   partial_dependence=plan.get("partial_dependence"))
+                   partial_dependence=plan.get("partial_dependence"), staged=plan.get("staged_scores"))
     received = utc_iso()
     slice_key = ",".join(str(int(c)) for c in cand_ids)
     gpu = dd.device.index if dd.is_gpu else None

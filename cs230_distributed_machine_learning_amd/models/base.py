@@ -36,6 +36,10 @@ class FitTask:
     # resolved it -- a kept fit also computes one-way partial dependence on its training rows
     # (models/forest.py _attach_pd)
     partial_dependence: Optional[Dict[str, Any]] = None
+    # GradientBoosting*: {"scoring"} -- the job's train_params["staged_scores"] as
+    # service.staged_options resolved it: the fit also records its held-out score and loss after
+    # every stage, FitOutput.info["staged"] (models/boosting.py, docs/GBRT_STAGED.md)
+    staged: Optional[Dict[str, Any]] = None
 
 
 @dataclass

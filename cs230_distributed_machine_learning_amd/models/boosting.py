@@ -37,7 +37,7 @@ from typing import Any, Dict, List, Optional
 import numpy as np
 import torch
 
-from ..ops import forest_ops
+from ..ops import forest_ops, gbrt_ops
 from ..search import cv as cv_mod
 from ..utils import native
 from .base import (Family, FitOutput, FitTask, ParamError, as_bool, as_float, as_int, prefix_groups, register,
@@ -60,6 +60,7 @@ _DEFAULTS = {
     "n_iter_no_change": None, "tol": 1e-4, "ccp_alpha": 0.0,
 }
 _F32_EPS = float(np.finfo(np.float32).eps)
+STAGED_SHARDED = "staged_scores is not computed for row-sharded jobs (run with parallelism='task')"
 
 
 def _max_features(v, d):
@@ -385,7 +386,9 @@ class GradientBoostingFamily(Family):
         return out
 
     def _boost(self, data, batch: List[FitTask], K: int, keep_models: bool,
-               follow: Optional[Dict[int, List[FitTask]]] = None) -> List[FitOutput]:
+               follow: Optional[Dict[int, List[FitTask]]] = None, want_masks: bool = False) -> List[FitOutput]:
+        """``want_masks`` (tests only): every recorded fit's output also carries its per-stage
+        in-bag masks, ``info["masks"]`` bool [stages, n]."""
         t0 = time.perf_counter()
         # prefix fits (prefix_groups): raw scores of leader f after its first m stages
         follow = follow or {}
@@ -403,6 +406,16 @@ class GradientBoostingFamily(Family):
         train = data.roles[split_idx] == 1                                  # [F, n]
         clf = data.classification
         sharded = getattr(data, "is_row_shard", False)
+        # per-stage statistics (ops/gbrt_ops.py, docs/GBRT_STAGED.md): a kept fit records the loss of
+        # its in-bag and out-of-bag rows after every stage (train_score_, oob_scores_), a fit of a job
+        # with staged_scores also the score and loss of its held-out rows; other fits launch nothing
+        group = [[t] + follow.get(t.task_id, []) for t in batch]
+        rec_keep = [keep_models and keep_fit[f] and not sharded for f in range(F)]
+        rec = [not sharded and (rec_keep[f] or any(g.staged is not None for g in group[f])) for f in range(F)]
+        rec_ids = [f for f in range(F) if rec[f]]
+        slot = {f: i for i, f in enumerate(rec_ids)}
+        masks: Dict[int, List[Any]] = {f: [] for f in rec_ids} if want_masks else {}
+        fi_rows: Dict[int, List[Any]] = {f: [] for f in range(F) if rec_keep[f]}
         if sharded:
             # the held-out early-stopping split is not a sum over ranks; leaf percentiles are,
             # as byte histograms of the fused stage's radix select (GPU only)
@@ -488,6 +501,34 @@ class GradientBoostingFamily(Family):
             slot_sum_all = torch.empty((F * K, S, 2), dtype=torch.float64, device=dev)
             slot_node_all = torch.empty((F * K, S), dtype=torch.int32, device=dev)
             slot_val_all = torch.empty((F * K, S), dtype=torch.float64, device=dev)
+        if rec_ids:
+            # stats[slot][0] is taken before the first stage (sklearn's initial_loss of a subsampled
+            # fit), stats[slot][s + 1] after stage s; read back once, after the loop
+            stats = gbrt_ops.new_stats(len(rec_ids), max(n_est[f] for f in rec_ids) + 1, dev)
+            st_part = torch.empty(gbrt_ops.part_words(n, len(rec_ids)), dtype=torch.int64, device=dev)
+            if fused:
+                st_y = ycls32 if clf else yreg64
+            else:
+                st_y = data.y_cls.to(torch.int32).contiguous() if clf else data.y_reg.double().contiguous()
+            st_roles = data.roles.contiguous()
+            val_fits = [f for f in rec_ids if f in val_rows]
+            val_row = {f: i for i, f in enumerate(val_fits)}
+            st_val = None
+            if val_fits:
+                st_val = torch.zeros((len(val_fits), n), dtype=torch.uint8, device=dev)
+                for f in val_fits:
+                    st_val[val_row[f], val_rows[f]] = 1
+            alpha_of = [float(t.params.get("alpha", 0.9)) for t in batch]
+
+            def stats_plan(act, pick, n_delta):
+                """The launch plan of the recorded fits at positions ``pick`` of the active set."""
+                fs = [act[a] for a in pick]
+                return gbrt_ops.stats_plan(
+                    [f * K for f in fs], [batch[f].params["loss"] for f in fs], [batch[f].split for f in fs],
+                    [a * K for a in pick], [val_row.get(f, -1) for f in fs], [slot[f] for f in fs], list(pick),
+                    [alpha_of[f] for f in fs], K=K, raw_rows=F * K, role_rows=int(st_roles.shape[0]),
+                    inbag_rows=len(act) * K, val_rows=len(val_fits), stat_fits=len(rec_ids), delta_len=n_delta,
+                    device=dev)
         if sharded:   # the global training rows (ascending), for subsample draws equal on every rank
             cnts = [data.all_gather_equal(torch.tensor([int(ti.numel())], device=dev)).cpu().numpy() for ti in train_idx]
             gtrain = [data._gather_rows(ti + data.r0, c) for ti, c in zip(train_idx, cnts)]
@@ -575,6 +616,26 @@ class GradientBoostingFamily(Family):
                 if not sub_rows:
                     cst["roles_t"] = roles_t
             tgt = T32[:J] if fused else G.reshape(J, n).float().contiguous()
+            if rec_ids:
+                st_pick = [a for a, f in enumerate(act) if rec[f]]
+                st_delta = None
+                if fused:
+                    if pct_any:
+                        st_delta = fit_delta
+                elif any(batch[act[a]].params["loss"] == LOSS_HUBER for a in st_pick):
+                    st_delta = torch.tensor([float(hub_delta.get(f) or 0.0) for f in act], dtype=torch.float64,
+                                            device=dev)
+                n_delta = F if fused else A
+                st_plan = cst.get("stats_plan")
+                if st_plan is None:
+                    st_plan = cst["stats_plan"] = stats_plan(act, st_pick, n_delta)
+                if stage == 0:   # subsampled fits: the loss before the first stage, on stage 0's draw
+                    first = [a for a in st_pick if batch[act[a]].params["subsample"] < 1.0]
+                    if first:
+                        gbrt_ops.stage_stats(raw, st_y, st_roles, roles_t, st_val, stats_plan(act, first, n_delta),
+                                             st_delta, stats, 0, st_part)
+                for a in (st_pick if want_masks else ()):
+                    masks[act[a]].append(inbag[a].clone())
             specs = _stage_specs(batch, act, K, seeds, stage)
             limit = np.repeat([batch[f].params.get("max_leaf_nodes", 0) for f in act], K)
             ccp = np.repeat([batch[f].params.get("ccp_alpha", 0.0) for f in act], K)
@@ -663,6 +724,8 @@ class GradientBoostingFamily(Family):
                 # --- raw-score update of every row (train and held-out) --------------------
                 upd = value[leaf].view(A, K, n) * lr[act_t].view(A, 1, 1)
                 raw[act_t] += upd
+            if rec_ids and st_pick:   # the stage's statistics of every recorded fit: one launch, no read-back
+                gbrt_ops.stage_stats(raw, st_y, st_roles, roles_t, st_val, st_plan, st_delta, stats, stage + 1, st_part)
             for a, f in enumerate(act):
                 if f in val_rows:
                     vl = self._val_loss(batch[f].params, raw[f][:, val_rows[f]], val_rows[f], data, K, hub_delta.get(f))
@@ -679,18 +742,50 @@ class GradientBoostingFamily(Family):
                         continue
                     lr_f = float(lr[f])
                     kept[f].append([_extract_tree(nodes_np, vals_np * lr_f, a * K + k) for k in range(K)])
+                # mean decrease in impurity: the un-normalised row of every kept tree of the stage,
+                # summed over the fit's trees with more than one node (and their count)
+                kept_a = [a for a, f in enumerate(act) if rec_keep[f]]
+                if kept_a:
+                    roots = np.concatenate([np.arange(a * K, (a + 1) * K) for a in kept_a])
+                    rows_t, multi_t = forest_ops.feature_importances(nodes_np, vals.cpu().numpy(), J, data.d, True,
+                                                                     forest_ops.FRIEDMAN, per_tree=True, roots=roots)
+                    rows_np = rows_t.numpy().reshape(len(kept_a), K, data.d)
+                    multi_np = multi_t.numpy().reshape(len(kept_a), K)
+                    for i, a in enumerate(kept_a):
+                        fi_rows[act[a]].append((rows_np[i][multi_np[i]].sum(0), int(multi_np[i].sum())))
             for f in act:   # prefix fits that end at this stage
                 for fo in checkpoints.get(f, {}).get(stage + 1, []):
                     snaps.append((fo, f, raw[f].clone()))
         if gpu:
             torch.cuda.synchronize(dev)
         dt = time.perf_counter() - t0
-        outs = self._outputs(batch, raw, init, kept, data, K, clf, keep_models, dt)
+        extras = None
+        if rec_ids or sharded:
+            curves: Dict[int, Dict[str, Any]] = {}
+            if rec_ids:
+                st_host = stats.cpu().numpy()
+                for f in rec_ids:
+                    opts = next((g.staged for g in group[f] if g.staged is not None), None)
+                    ss_tot = float("nan")
+                    if opts is not None and not clf:
+                        yt = data.y_reg[data.test_rows[batch[f].split].long()].double()
+                        ss_tot = float(((yt - yt.mean()) ** 2).sum()) if yt.numel() else 0.0
+                    curves[f] = gbrt_ops.stage_curves(st_host[slot[f], :n_est[f] + 1], batch[f].params["loss"], K,
+                                                      (opts or {}).get("scoring"), ss_tot)
+                    if want_masks:
+                        curves[f]["masks"] = torch.stack(masks[f])[:n_est[f]].cpu().numpy()
+
+            def extra_of(t: FitTask, f: int, m: int) -> Dict[str, Any]:
+                return _fit_extras(t, curves.get(f), m, fi_rows.get(f), keep_models and t.keep, sharded)
+
+            extras = [extra_of(t, f, n_est[f]) for f, t in enumerate(batch)]
+        outs = self._outputs(batch, raw, init, kept, data, K, clf, keep_models, dt, extras)
         if snaps:
             outs += self._outputs([s[0] for s in snaps], torch.stack([s[2] for s in snaps]),
                                   torch.stack([init[s[1]] for s in snaps]),
                                   [kept[s[1]][:s[0].params["n_estimators"]] for s in snaps], data, K, clf,
-                                  keep_models, dt)
+                                  keep_models, dt,
+                                  [extra_of(s[0], s[1], s[0].params["n_estimators"]) for s in snaps] if extras else None)
         return outs
 
     @staticmethod
@@ -767,7 +862,7 @@ class GradientBoostingFamily(Family):
         return value
 
     @staticmethod
-    def _outputs(batch, raw, init, kept, data, K, clf, keep_models, dt) -> List[FitOutput]:
+    def _outputs(batch, raw, init, kept, data, K, clf, keep_models, dt, extras=None) -> List[FitOutput]:
         F = len(batch)
         outs = []
         for f, t in enumerate(batch):
@@ -789,6 +884,13 @@ class GradientBoostingFamily(Family):
                           info={"warnings": t.params.get("warnings", [])})
             if keep_models and t.keep:
                 o.model = _pack_model(kept[f], init[f].cpu().numpy(), t, data, K)
+            ex = extras[f] if extras else None
+            if ex:   # per-stage curves and importances (_fit_extras)
+                o.info.update(ex["info"])
+                if ex["warnings"]:
+                    o.info["warnings"] = list(o.info["warnings"]) + ex["warnings"]
+                if o.model is not None:
+                    o.model.update(ex["model"])
             outs.append(o)
         return outs
 
@@ -839,6 +941,49 @@ class GradientBoostingFamily(Family):
         # huber: delta = alpha-percentile of |y - raw| over the fit's training rows (set_huber_delta)
         delta = float(_percentile_icdf(diff[train_row].abs(), rp["alpha"]))
         return torch.where(diff.abs() <= delta, diff, delta * torch.sign(diff)).view(1, -1), delta
+
+
+def _fit_extras(t: FitTask, curves: Optional[Dict[str, Any]], m: int, fi_rows, kept: bool,
+                sharded: bool) -> Dict[str, Any]:
+    """What one fit (a leader, or a prefix follower cut to its own ``m`` stages) reports beyond its
+    predictions: ``info["staged"]`` for a job with staged_scores, and for a kept fit the artefact's
+    ``train_score`` / ``oob_*`` / ``feature_importances`` (sklearn's ``_fit_stages`` recurrences:
+    ``curves`` index 0 is the state before the first stage, index s + 1 the state after stage s)."""
+    out: Dict[str, Any] = {"info": {}, "model": {}, "warnings": []}
+    if sharded:
+        if t.staged is not None:
+            out["warnings"].append(STAGED_SHARDED)
+        return out
+    if curves is None:
+        return out
+    train = curves["train_loss"][1:m + 1].copy()
+    if t.staged is not None:
+        out["info"]["staged"] = {"score": curves["test_score"][1:m + 1].tolist(),
+                                 "loss": curves["test_loss"][1:m + 1].tolist(), "train_loss": train.tolist(),
+                                 "scoring": curves["scoring"]}
+    if "masks" in curves:
+        out["info"]["masks"] = curves["masks"][:m]
+    if kept:
+        mod = out["model"]
+        mod["train_score"] = train
+        if t.params["subsample"] < 1.0:
+            oob = curves["oob_loss"][1:m + 1].copy()
+            mod["oob_scores"] = oob
+            mod["oob_improvement"] = curves["oob_loss"][0:m] - oob   # previous (or initial) loss - this stage's
+            mod["oob_score"] = float(oob[-1])
+        if fi_rows is not None:
+            acc = np.zeros_like(fi_rows[0][0]) if fi_rows else np.zeros(0)
+            cnt = 0
+            for row, c in fi_rows[:m]:
+                acc = acc + row
+                cnt += c
+            mean = acc / cnt if cnt else acc
+            tot = float(mean.sum())
+            mod["feature_importances"] = mean / tot if tot > 0 else mean
+        if t.staged is not None:
+            mod["staged_test_score"] = curves["test_score"][1:m + 1].copy()
+            mod["staged_test_loss"] = curves["test_loss"][1:m + 1].copy()
+    return out
 
 
 def _stage_specs(batch, act: List[int], K: int, seeds: List[int], stage: int) -> np.ndarray:
@@ -930,7 +1075,9 @@ def _pack_model(stages, init: np.ndarray, t: FitTask, data, K: int) -> Dict[str,
     }
 
 
-def gbrt_raw_numpy(model: Dict[str, Any], X: np.ndarray) -> np.ndarray:
+def gbrt_staged_raw_numpy(model: Dict[str, Any], X: np.ndarray, copy: bool = True):
+    """sklearn's ``_staged_raw_predict``: the raw scores [n, K] after every stage, one stage per
+    step (``copy=False``: the same array every step, updated in place)."""
     lib = native.cpu_lib()
     X = np.ascontiguousarray(X, dtype=np.float32)
     edges = np.ascontiguousarray(model["edges"], dtype=np.float32)
@@ -952,6 +1099,15 @@ def gbrt_raw_numpy(model: Dict[str, Any], X: np.ndarray) -> np.ndarray:
                 go = Xb[rows, feat] > b
                 node = np.where(inner, nodes[node, 1] + go, node)
             raw[:, k] += value[node]
+        yield raw.copy() if copy else raw
+
+
+def gbrt_raw_numpy(model: Dict[str, Any], X: np.ndarray) -> np.ndarray:
+    raw = None
+    for raw in gbrt_staged_raw_numpy(model, X, copy=False):
+        pass
+    if raw is None:   # no stage: the initial prediction
+        raw = np.tile(np.asarray(model["init"], dtype=np.float64), (np.asarray(X).shape[0], 1))
     return raw
 
 

@@ -1282,7 +1282,8 @@ def partial_dependence_values(fb: ForestBuild, Xb, t0: int, t1: int, rows, featu
     return res
 
 
-def feature_importances(nodes, vals, n_trees: int, d: int, is_reg: bool, criterion: int) -> np.ndarray:
+def feature_importances(nodes, vals, n_trees: int, d: int, is_reg: bool, criterion: int, per_tree: bool = False,
+                        roots=None):
     """sklearn's ``feature_importances_`` (mean decrease in impurity) of trees rooted at nodes
     0 .. n_trees-1 of a pool: float64 [d].
 
@@ -1292,7 +1293,13 @@ def feature_importances(nodes, vals, n_trees: int, d: int, is_reg: bool, criteri
     impurities come from ``vals`` as ``prune_ccp`` computes them (gini, entropy in log2,
     sum wy^2 / W - mean^2 for squared_error / friedman_mse), so bootstrap and class weights
     are in.  Works on either device, one vectorised step per tree level (no per-node host
-    loop).  ``poisson`` / ``absolute_error``: the pool does not hold their impurities."""
+    loop).  ``poisson`` / ``absolute_error``: the pool does not hold their impurities.
+
+    ``per_tree=True`` returns instead (rows float64 [T, d], multi bool [T]) as tensors on the
+    pool's device: every tree's UN-normalised row (sklearn ``compute_feature_importances(
+    normalize=False)``) and whether the tree has more than one node -- GradientBoosting averages
+    those rows over its trees (models/boosting.py).  ``roots`` (with ``per_tree``): the root nodes
+    of the trees to take, instead of nodes 0 .. n_trees-1."""
     if criterion not in (GINI, ENTROPY, MSE, FRIEDMAN):
         raise ValueError("feature importances need the gini, entropy, squared_error or friedman_mse impurity")
     nodes = torch.from_numpy(np.ascontiguousarray(nodes)) if not isinstance(nodes, torch.Tensor) else nodes
@@ -1314,19 +1321,27 @@ def feature_importances(nodes, vals, n_trees: int, d: int, is_reg: bool, criteri
         del p
     wi = w * imp
     del imp, v
+    if per_tree and roots is not None:
+        root = torch.as_tensor(roots, dtype=torch.int64, device=dev).reshape(-1)
+        T = int(root.numel())
+    else:
+        root = torch.arange(T, dtype=torch.int64, device=dev)
     acc = torch.zeros(T * d, dtype=torch.float64, device=dev)
-    fo = torch.arange(T, dtype=torch.int64, device=dev)
-    tr = fo.clone()
+    fo = root.clone()
+    tr = torch.arange(T, dtype=torch.int64, device=dev)
+    w_root = w[root]
     while fo.numel():
         rec = nodes[fo]
         internal = rec[:, 0] >= 0
         fi, tr = fo[internal], tr[internal]
         l = rec[internal, 1].to(torch.int64)
         feat = rec[internal, 0].to(torch.int64) >> 8
-        acc.index_add_(0, tr * d + feat, (wi[fi] - wi[l] - wi[l + 1]) / w[tr])   # w[tr]: the tree's root weight
+        acc.index_add_(0, tr * d + feat, (wi[fi] - wi[l] - wi[l + 1]) / w_root[tr])   # the tree's root weight
         tr = tr.repeat_interleave(2)
         fo = torch.stack([l, l + 1], 1).reshape(-1)
     per = acc.view(T, d)
+    if per_tree:
+        return per, nodes[root, 0] >= 0
     s = per.sum(1, keepdim=True)
     per = torch.where(s > 0, per / s.clamp_min(1e-300), per)
     multi = nodes[:T, 0] >= 0   # trees with more than one node

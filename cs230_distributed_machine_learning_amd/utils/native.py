@@ -128,6 +128,12 @@ GbStageArgs = _i64_struct(
 )
 GbGradArgs = _i64_struct("GbGradArgs", ["n", "K", "A", "fit_raw", "fit_loss", "raw", "ycls", "yreg", "grad", "tgt",
                                         "fit_alpha", "fit_delta", "fit_train", "sel_hist", "sel_state"])
+# csrc/kernels/gbrt.hip GbStatsArgs (per-stage loss / score statistics of the recorded fits)
+GbStatsArgs = _i64_struct(
+    "GbStatsArgs",
+    ["n", "K", "A", "raw", "ycls", "yreg", "roles", "inbag", "val", "fit_raw", "fit_loss", "fit_role", "fit_inbag",
+     "fit_val", "fit_out", "fit_dpos", "fit_alpha", "delta", "part", "stats", "stage", "n_stages"],
+)
 # csrc/kernels/forest_mae.hip (criterion="absolute_error" builder)
 MaeArgs = _i64_struct(
     "MaeArgs",
@@ -178,6 +184,8 @@ def cpu_lib() -> ctypes.CDLL:
                                               c_i32, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_i64, c_i32, c_i32, c_vp,
                                               c_vp, c_vp, c_vp]
             lib.dml_cpu_bin.argtypes = [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64]
+            lib.dml_cpu_gbrt_stage_stats.restype = None
+            lib.dml_cpu_gbrt_stage_stats.argtypes = [c_i64, c_i64, c_i64] + [c_vp] * 17 + [c_i64, c_i64]
             lib.dml_cpu_svm_sizeof_prob.restype = c_i32
             lib.dml_cpu_svm_smo.argtypes = [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]
             lib.dml_cpu_svm_platt_fit.restype = c_i32
@@ -291,6 +299,8 @@ def _register_optional(lib) -> None:
         "dml_gb_stage_phase": (c_i32, [ctypes.POINTER(GbStageArgs), c_vp]),
         "dml_gb_sel_step": (c_i32, [ctypes.POINTER(GbStageArgs), c_i32, c_i32, c_vp]),
         "dml_gb_fit_sel_step": (c_i32, [ctypes.POINTER(GbGradArgs), c_i32, c_i32, c_vp]),
+        "dml_gb_sizeof_stats_args": (c_i32, []),
+        "dml_gb_stage_stats": (c_i32, [ctypes.POINTER(GbStatsArgs), c_vp]),
         "dml_exp_hist": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
         "dml_forest_release_scratch": (c_i32, []),
         "dml_forest_block_stash_planes": (c_i32, []),
@@ -310,6 +320,9 @@ def _register_optional(lib) -> None:
         if (lib.dml_gb_sizeof_stage_args() != ctypes.sizeof(GbStageArgs)
                 or lib.dml_gb_sizeof_grad_args() != ctypes.sizeof(GbGradArgs)):
             raise RuntimeError("GBRT stage argument layout mismatch between HIP library and Python")
+    if (getattr(lib, "dml_gb_sizeof_stats_args", None) is not None
+            and lib.dml_gb_sizeof_stats_args() != ctypes.sizeof(GbStatsArgs)):
+        raise RuntimeError("GBRT stage statistics argument layout mismatch between HIP library and Python")
     if getattr(lib, "dml_mae_sizeof_args", None) is not None and lib.dml_mae_sizeof_args() != ctypes.sizeof(MaeArgs):
         raise RuntimeError("MAE builder argument layout mismatch between HIP library and Python")
     if getattr(lib, "dml_lr_sizeof_fwd_args", None) is not None:
