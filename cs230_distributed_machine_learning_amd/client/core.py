@@ -75,6 +75,21 @@ class _LocalTransport:
         raise ValueError(f"unknown endpoint {endpoint}")
 
 
+def _encode_scoring(scoring):
+    """``scoring`` as it travels: a list, tuple or dict of scorer names survives the JSON round
+    trip as it is (a tuple arrives as a list, a dict keeps its order); a callable has no wire form
+    and is marked, so the service can refuse it by name instead of reading its ``str()``."""
+    if callable(scoring):
+        return {"__callable__": getattr(scoring, "__name__", None) or type(scoring).__name__}
+    if isinstance(scoring, dict):
+        return {k: _encode_scoring(v) for k, v in scoring.items()}
+    if isinstance(scoring, (list, tuple)):
+        return [_encode_scoring(v) for v in scoring]
+    if isinstance(scoring, (set, frozenset)):
+        return {"__set__": sorted(str(v) for v in scoring)}
+    return scoring
+
+
 class MLTaskManager:
     def __init__(self, url: Optional[str] = None, controller=None, timeout: float = 30.0):
         self.api_url = url.rstrip("/") if url else None
@@ -198,6 +213,9 @@ class MLTaskManager:
                           "n_iter": estimator.n_iter, "random_state": rs if isinstance(rs, (int, type(None))) else None}
             cv_params = {k: getattr(estimator, k, None) for k in
                          ("cv", "scoring", "refit", "verbose", "error_score", "return_train_score")}
+            cv_params["scoring"] = _encode_scoring(cv_params["scoring"])
+            if callable(cv_params["refit"]):
+                cv_params["refit"] = _encode_scoring(cv_params["refit"])
             hyper = {"base_estimator_params": {k.split("__")[-1]: v for k, v in base.get_params().items()},
                      "search_params": search, "cv_params": cv_params}
             return {"model_type": model_type, "search_type": search_type, "hyperparameters": hyper}

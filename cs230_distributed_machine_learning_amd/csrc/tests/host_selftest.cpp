@@ -3,7 +3,8 @@
 // tests/test_host_sanitizers.py.  The reference has no race detection or sanitizers
 // (SURVEY §5.2); this covers every entry point the Python layer calls through ctypes:
 // tree building (gini / entropy / mse, bootstrap on/off, depth limits), export, leaf
-// apply, threshold refinement, batched predict, binning, LPT placement and chunking.
+// apply, threshold refinement, batched predict, binning, LPT placement and chunking, per-fit
+// score statistics.
 // Exit status 0 = all invariants hold and the sanitizers saw nothing.
 #include <cmath>
 #include <cstdint>
@@ -32,6 +33,9 @@ void dml_cpu_bin(const float*, int64_t, int64_t, const float*, uint8_t*, int64_t
 double dml_lpt_assign(const double*, const double*, int64_t, const double*, const double*, const double*, int64_t,
                       int32_t*);
 int64_t dml_chunk_units(const double*, int64_t, double, int64_t, int32_t*);
+int dml_cpu_fit_stats_tile();
+int dml_cpu_fit_stats(const int32_t*, const int64_t*, const void*, const int32_t*, const float*, int64_t, int64_t,
+                      int64_t, int64_t, int64_t, double*, void*);
 }
 
 static int g_fail = 0;
@@ -196,7 +200,66 @@ static void sched_case() {
   CHECK(dml_chunk_units(costs.data(), 0, 3.0, 1, chunk.data()) == 0);
 }
 
+// per-fit score statistics (runtime/score_stats_cpu.cpp): unequal fits, an empty fit, a fit
+// longer than a tile, C = 3, an uncountable prediction and a row id outside the targets
+static void fit_stats_case() {
+  const int64_t n = 500, C = 3, tile = dml_cpu_fit_stats_tile();
+  const int64_t lens[] = {0, 1, 257, tile + 1, 64};
+  const int64_t F = 5;
+  std::vector<int64_t> off(F + 1, 0);
+  for (int64_t f = 0; f < F; ++f) off[f + 1] = off[f] + lens[f];
+  const int64_t total = off[F], max_rows = tile + 1;
+  std::vector<int32_t> rows(total), pcls(total), ycls(n);
+  std::vector<float> preg(total), yreg(n);
+  for (int64_t r = 0; r < n; ++r) { ycls[r] = (int32_t)(rnd() % C); yreg[r] = 0.5f + rndf(); }
+  for (int64_t i = 0; i < total; ++i) {
+    rows[i] = (int32_t)(rnd() % n);
+    pcls[i] = (int32_t)(rnd() % C);
+    preg[i] = 0.5f + rndf();
+  }
+  pcls[off[2] + 5] = 7;           // outside [0, C)
+  rows[off[3] + 9] = (int32_t)n;  // outside the targets
+  std::vector<int64_t> cm(F * (C * C + 1), -1);
+  CHECK(dml_cpu_fit_stats(rows.data(), off.data(), pcls.data(), ycls.data(), nullptr, n, C, F, max_rows, 0, nullptr,
+                          cm.data()) == 0);
+  for (int64_t f = 0; f < F; ++f) {
+    std::vector<int64_t> ref(C * C + 1, 0);
+    for (int64_t i = off[f]; i < off[f + 1]; ++i) {
+      const bool ok = rows[i] < n && pcls[i] >= 0 && pcls[i] < C;
+      ref[ok ? ycls[rows[i]] * C + pcls[i] : C * C] += 1;
+    }
+    for (int64_t j = 0; j <= C * C; ++j) CHECK(cm[f * (C * C + 1) + j] == ref[j]);
+  }
+  CHECK(cm[2 * (C * C + 1) + C * C] == 1 && cm[3 * (C * C + 1) + C * C] == 1);
+  const int64_t gx = (max_rows + tile - 1) / tile;
+  std::vector<double> part(F * gx * 14, -1.0), st(F * 14, -1.0), st0(F * 14, -1.0);
+  CHECK(dml_cpu_fit_stats(rows.data(), off.data(), preg.data(), nullptr, yreg.data(), n, 0, F, max_rows, 7, part.data(),
+                          st.data()) == 0);
+  CHECK(dml_cpu_fit_stats(rows.data(), off.data(), preg.data(), nullptr, yreg.data(), n, 0, F, max_rows, 0, nullptr,
+                          st0.data()) == 0);
+  for (int64_t f = 0; f < F; ++f) {
+    double cnt = 0.0, sy = 0.0, se2 = 0.0, mx = 0.0;
+    for (int64_t i = off[f]; i < off[f + 1]; ++i) {
+      if (rows[i] >= n) continue;
+      const double y = yreg[rows[i]], e = (double)preg[i] - y;
+      cnt += 1.0; sy += y; se2 += e * e; mx = std::fmax(mx, std::fabs(e));
+    }
+    const double* s = &st[f * 14];
+    CHECK(s[0] == cnt && s[6] == mx);
+    CHECK(std::fabs(s[1] - sy) <= 1e-12 * (1.0 + std::fabs(sy)) && std::fabs(s[4] - se2) <= 1e-12 * (1.0 + se2));
+    CHECK(s[9] == 0.0 && s[11] == 0.0 && s[13] == 0.0);
+    CHECK(lens[f] == 0 || s[8] >= 0.0);
+    for (int j = 0; j < 14; ++j) {
+      const bool logslot = j == 8 || j == 10 || j == 12;
+      CHECK(st0[f * 14 + j] == (logslot ? 0.0 : s[j]));
+    }
+  }
+  CHECK(dml_cpu_fit_stats(rows.data(), off.data(), pcls.data(), ycls.data(), nullptr, n, 65, F, max_rows, 0, nullptr,
+                          cm.data()) == 2);
+}
+
 int main() {
+  fit_stats_case();
   forest_case(false, kGini);
   forest_case(false, kEntropy);
   forest_case(true, kMSE);

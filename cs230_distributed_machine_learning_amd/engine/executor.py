@@ -39,7 +39,10 @@ class JobSpec:
     model_type: str
     candidates: List[Dict[str, Any]]          # full estimator params per candidate (base + point)
     cv: int = 5
-    scoring: Optional[str] = None
+    # a scorer name, or for a multi-metric job the resolved (label, scorer name) pairs
+    # (service.job_plan scoring_labels / scoring_names) with ``refit_metric`` naming the primary label
+    scoring: Any = None
+    refit_metric: Optional[str] = None
     holdout: bool = True
     test_size: Any = 0.2
     random_state: Any = 42
@@ -141,6 +144,63 @@ def _scores_for(data, task: FitTask, out: FitOutput, scorer: str, pre: Optional[
     return scoring_mod.score(scorer, y, out.pred, data.n_classes, out.proba, decision=out.decision)
 
 
+def _multi_scores(data, tasks, outputs: Dict[int, FitOutput], pairs, clf: bool) -> Dict[int, Dict[str, float]]:
+    """Every metric of a multi-metric job for every successful fit, CV and holdout together:
+    {task_id: {label: score}}.  The predictions of the whole family batch are stacked and
+    ``scoring.fit_statistics`` runs once (one launch, one device->host read); every metric in
+    ``scoring.STAT_SCORERS`` is derived from that read-back.  The probability, ranking and median
+    scorers go through ``scoring.score`` per fit, as in a single-metric job -- and so does a fit
+    whose predictions are not the kernel's types (float64 regression predictions are scored in
+    float64, not rounded to float32), and every fit of a row-sharded table (its resident targets
+    are one rank's)."""
+    y_all = data.y_cls if clf else data.y_reg
+    C = int(data.n_classes) if clf else 0
+    stat_names = sorted({nm for _l, nm in pairs if nm in scoring_mod.STAT_SCORERS})
+    if getattr(data, "is_row_shard", False):
+        stat_names = []
+    live, batched = [], []
+    for t in tasks:
+        o = outputs.get(t.task_id)
+        if o is None or o.error or not isinstance(o.pred, torch.Tensor):
+            continue
+        live.append(t)
+        p = o.pred
+        fits = p.numel() == data.test_rows[t.split].numel() and p.device == y_all.device
+        typed = (not p.is_floating_point() and C >= 2) if clf else p.dtype == torch.float32
+        if stat_names and fits and typed:
+            batched.append(t)
+    stats: Dict[int, Any] = {}
+    if batched:
+        rows = torch.cat([data.test_rows[t.split] for t in batched])
+        preds = [outputs[t.task_id].pred.reshape(-1) for t in batched]
+        pred = torch.cat([p.to(torch.int32) for p in preds] if clf else preds)
+        off = np.concatenate([[0], np.cumsum([p.numel() for p in preds])]).astype(np.int64)
+        st = scoring_mod.fit_statistics(rows, off, pred, y_all, C, want=scoring_mod.stats_want(stat_names))
+        stats = {t.task_id: st[i] for i, t in enumerate(batched)}
+    res: Dict[int, Dict[str, float]] = {}
+    for t in live:
+        o = outputs[t.task_id]
+        y = None
+        vals: Dict[str, float] = {}
+        for label, nm in pairs:
+            if nm in scoring_mod.STAT_SCORERS and t.task_id in stats:
+                vals[label] = scoring_mod.score_from_stats(nm, stats[t.task_id], data.n_classes)
+            else:
+                if y is None:
+                    y = data.test_targets(t.split)
+                vals[label] = scoring_mod.score(nm, y, o.pred, data.n_classes, o.proba, decision=o.decision)
+        res[t.task_id] = vals
+    return res
+
+
+def _cv_summary(cv_scores: List[float], error_score) -> tuple:
+    """(mean_cv_score, std_cv_score) of one metric's fold scores."""
+    finite = [x for x in cv_scores if x is not None and not math.isnan(x)]
+    mean = float(np.mean(cv_scores)) if len(finite) == len(cv_scores) else (
+        float(np.mean(finite)) if finite and error_score is None else float("nan"))
+    return mean, (float(np.std(cv_scores)) if finite else float("nan"))
+
+
 def run_candidates(data, spec: JobSpec, candidate_ids: Sequence[int]) -> List[CandidateResult]:
     """Run every split of the given candidates; returns one result per candidate."""
     with trace.range("run_prepare"):
@@ -148,11 +208,20 @@ def run_candidates(data, spec: JobSpec, candidate_ids: Sequence[int]) -> List[Ca
     clf = is_classifier(spec.model_type)
     fam = family_of(spec.model_type)
     self_scored = spec.model_type in getattr(fam, "self_scored", ())
+    pairs = None   # multi-metric: (label, scorer name) in the order asked
     if self_scored:
         # estimators scored by their own ``score`` method (sklearn GridSearchCV with scoring=None)
         if spec.scoring not in (None, "None", "", "score"):
             raise ValueError(f"scoring {spec.scoring!r} needs predictions; {spec.model_type} only has score()")
         scorer = "score"
+    elif isinstance(spec.scoring, (list, tuple)):
+        pairs = [(str(label), scoring_mod.validate_scoring(nm, clf)) for label, nm in spec.scoring]
+        if not pairs:
+            raise ValueError("multi-metric scoring needs at least one metric")
+        primary = spec.refit_metric if spec.refit_metric is not None else pairs[0][0]
+        if primary not in dict(pairs):
+            raise ValueError(f"refit metric {primary!r} is not one of the scorer keys {[lb for lb, _n in pairs]}")
+        scorer = dict(pairs)[primary]   # the single-metric keys of the result describe the primary metric
     else:
         scorer = scoring_mod.validate_scoring(spec.scoring, clf)
     if not clf and not self_scored and not getattr(data, "y_is_numeric", True):
@@ -173,7 +242,18 @@ def run_candidates(data, spec: JobSpec, candidate_ids: Sequence[int]) -> List[Ca
         raise ValueError(f"{spec.model_type} has no row-sharded (data-parallel) fit; run it task-parallel")
     with trace.range("run_tasks"):
         tasks, errors = build_tasks(data, spec, candidate_ids)
-    if scoring_mod.needs_proba(scorer):   # families that only predict labels by default add probabilities
+    if pairs is not None:
+        from ..models.svm import _NOT_FROM_PROBA
+
+        # probabilities when any metric needs them; FitTask.scorer names one that reads
+        # FitOutput.proba if there is one, so svm._asks_proba is true exactly then
+        asks = [nm for _l, nm in pairs if scoring_mod.needs_proba(nm)]
+        if asks:
+            reads = [nm for nm in asks if nm not in _NOT_FROM_PROBA]
+            for t in tasks:
+                t.need_proba = True
+                t.scorer = reads[0] if reads else asks[0]
+    elif scoring_mod.needs_proba(scorer):   # families that only predict labels by default add probabilities
         for t in tasks:
             t.need_proba = True
             t.scorer = scorer
@@ -216,8 +296,13 @@ def run_candidates(data, spec: JobSpec, candidate_ids: Sequence[int]) -> List[Ca
         by_cand.setdefault(t.candidate, []).append(t)
     cv_idx = [i for i, n in enumerate(names) if n.startswith("cv")]
     hold_idx = names.index("holdout") if "holdout" in names else None
+    multi: Dict[int, Dict[str, float]] = {}
     with trace.range("run_scores"):
-        pre = _batched_scores(data, [t for t in tasks if t.split in cv_idx], outputs, scorer)
+        if pairs is not None:
+            multi = _multi_scores(data, tasks, outputs, pairs, clf)
+            pre = {tid: v[primary] for tid, v in multi.items()}
+        else:
+            pre = _batched_scores(data, [t for t in tasks if t.split in cv_idx], outputs, scorer)
     results: List[CandidateResult] = []
     for c in candidate_ids:
         if c in errors and c not in by_cand:
@@ -229,6 +314,7 @@ def run_candidates(data, spec: JobSpec, candidate_ids: Sequence[int]) -> List[Ca
         ts = by_cand.get(c, [])
         split_out = {t.split: (t, outputs.get(t.task_id)) for t in ts}
         cv_scores: List[float] = []
+        label_cv: Dict[str, List[float]] = {label: [] for label, _nm in pairs or ()}
         warnings: List[str] = []
         failed_fits = 0
         for s in cv_idx:
@@ -239,9 +325,13 @@ def run_candidates(data, spec: JobSpec, candidate_ids: Sequence[int]) -> List[Ca
                     results.append(_failed(c, spec, o.error if o else "fit failed"))
                     break
                 cv_scores.append(float(spec.error_score) if spec.error_score is not None else float("nan"))
+                for v in label_cv.values():   # a failed fold takes error_score for every metric
+                    v.append(cv_scores[-1])
                 continue
             with trace.range("run_scores"):
                 cv_scores.append(_scores_for(data, t, o, scorer, pre))
+            for label, v in label_cv.items():
+                v.append(multi[t.task_id][label])
             for w in o.info.get("warnings", []):
                 if w not in warnings:
                     warnings.append(w)
@@ -291,14 +381,26 @@ def run_candidates(data, spec: JobSpec, candidate_ids: Sequence[int]) -> List[Ca
                 R["training_time"] = fit_s
             if cv_idx:
                 R["cv_scores"] = cv_scores
-                finite = [x for x in cv_scores if x is not None and not math.isnan(x)]
-                R["mean_cv_score"] = float(np.mean(cv_scores)) if len(finite) == len(cv_scores) else (
-                    float(np.mean(finite)) if finite and spec.error_score is None else float("nan"))
-                R["std_cv_score"] = float(np.std(cv_scores)) if finite else float("nan")
+                R["mean_cv_score"], R["std_cv_score"] = _cv_summary(cv_scores, spec.error_score)
             else:
                 main = "score" if self_scored else ("accuracy" if clf else "r2_score")
                 R["cv_scores"] = []
                 R["mean_cv_score"] = R.get(main, float("nan"))
+            if pairs is not None:   # every metric, the primary one included (docs/MULTIMETRIC.md)
+                held = multi.get(split_out[hold_idx][0].task_id) if hold_idx is not None else None
+                R["scores"] = {}
+                for label, nm in pairs:
+                    e: Dict[str, Any] = {"scorer": nm, "cv_scores": label_cv[label]}
+                    if cv_idx:
+                        e["mean_cv_score"], e["std_cv_score"] = _cv_summary(label_cv[label], spec.error_score)
+                    else:   # no folds: the job ranks by the held-out score
+                        e["mean_cv_score"] = held[label] if held else float("nan")
+                        e["std_cv_score"] = float("nan")
+                    if held is not None:
+                        e["holdout_score"] = held[label]
+                    R["scores"][label] = e
+                if not cv_idx:
+                    R["mean_cv_score"] = R["scores"][primary]["mean_cv_score"]
             if spec.staged:
                 entry = staged_entry([split_out[s][1] for s in cv_idx], hold_out)
                 if entry is not None:

@@ -296,6 +296,9 @@ class JobTable:
                   for st in job.subtasks if st.status == "failed"]
         if failed:
             job.result["failed"] = failed
+        multi = multimetric_summary(job.request, ok)
+        if multi is not None:   # a job that does not ask carries no such key
+            job.result["multimetric"] = multi
         job.finished = True
         job.finished_ts = time.time()
 
@@ -378,6 +381,48 @@ def aggregate_best(results: List[Dict[str, Any]]) -> Optional[Dict[str, Any]]:
         return v
 
     return sorted(results, key=key, reverse=True)[0]
+
+
+def rank_test(means: List[Optional[float]]) -> List[int]:
+    """sklearn ``_format_results`` rank_test_*: ``rankdata(-mean, method="min")`` with NaN
+    (None after ``json_safe``) means replaced by ``nanmin - 1`` first, so they rank last; all-NaN
+    ranks every entry 1."""
+    import numpy as np
+
+    v = np.array([float("nan") if m is None else float(m) for m in means], dtype=np.float64)
+    if v.size == 0:
+        return []
+    if np.isnan(v).all():
+        return [1] * int(v.size)
+    v = np.where(np.isnan(v), np.nanmin(v) - 1, v)
+    return [int(1 + np.sum(-v < -x)) for x in v]   # min rank: 1 + the number of strictly better means
+
+
+def multimetric_summary(request: Dict[str, Any], results: List[Dict[str, Any]]) -> Optional[Dict[str, Any]]:
+    """``job_result["multimetric"]`` of a job whose ``scoring`` is a list, tuple or dict (None
+    otherwise): {"scoring": {label: scorer}, "refit": label or False, "rank_test": {label: [rank
+    per entry of ``results``]}}.  Derived from the request and the candidates' ``scores``, so a
+    job replayed from the journal reports the same."""
+    md = request.get("model_details") or {}
+    if md.get("search_type"):
+        cvp = (md.get("hyperparameters") or {}).get("cv_params") or {}
+        scoring, refit = cvp.get("scoring"), cvp.get("refit", True)
+    else:
+        tp = request.get("train_params") or {}
+        scoring, refit = tp.get("scoring"), tp.get("refit")
+    if isinstance(scoring, dict):
+        names = {str(k): v for k, v in scoring.items()}
+    elif isinstance(scoring, (list, tuple)):
+        names = {str(v): v for v in scoring}
+    else:
+        return None
+    if not names:
+        return None
+    if not isinstance(refit, str):
+        refit = False if md.get("search_type") else next(iter(names))
+    ranks = {label: rank_test([((r.get("scores") or {}).get(label) or {}).get("mean_cv_score") for r in results])
+             for label in names}
+    return {"scoring": names, "refit": refit, "rank_test": ranks}
 
 
 def _subtask_index(subtask_id: str) -> Optional[int]:

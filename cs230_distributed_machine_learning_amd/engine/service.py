@@ -181,6 +181,62 @@ def partial_dependence_options(tp: Dict[str, Any], model_type: str) -> Optional[
             "max_rows": None if mr is None else int(mr), "random_state": int(rs)}
 
 
+MULTI_FORMS = "a scorer name, a non-empty list or tuple of unique scorer names, or a dict {label: scorer name}"
+
+
+def multimetric_options(scoring, refit, model_type: str) -> Optional[Dict[str, Any]]:
+    """A list / tuple / dict ``scoring`` resolved to {"labels", "names", "refit_metric", "refit"};
+    None for a scorer name or no scoring (the single-metric path, unchanged).  Labels are the
+    result keys in the order given; ``refit`` must be one of them (the primary metric, refitted
+    like ``refit=True``) or False (no refit; the first label is primary)."""
+    from ..search import scoring as scoring_mod
+
+    if scoring is None or isinstance(scoring, str):
+        return None
+
+    def is_callable(v):   # client/core.py _encode_scoring marks what has no wire form
+        return callable(v) or (isinstance(v, dict) and "__callable__" in v)
+
+    if is_callable(scoring) or (isinstance(scoring, dict) and any(is_callable(v) for v in scoring.values())) or \
+            (isinstance(scoring, (list, tuple)) and any(is_callable(v) for v in scoring)):
+        raise ParamError(f"scoring: callables are not supported; scoring must be {MULTI_FORMS}")
+    if is_callable(refit):
+        raise ParamError("refit: callables are not supported; for multi-metric scoring refit must be a scorer key "
+                         "or False")
+    if isinstance(scoring, dict) and "__set__" in scoring:
+        raise ParamError(f"scoring must be {MULTI_FORMS}, got a set {scoring['__set__']!r}")
+    if isinstance(scoring, dict):
+        labels, names = [str(k) for k in scoring.keys()], list(scoring.values())
+    elif isinstance(scoring, (list, tuple)):
+        labels, names = [str(v) for v in scoring], list(scoring)
+        if len(set(labels)) != len(labels):
+            raise ParamError(f"scoring: the scorer names of a list must be unique, got {list(scoring)!r}")
+    else:
+        raise ParamError(f"scoring must be {MULTI_FORMS}, got {scoring!r}")
+    if not labels:
+        raise ParamError(f"scoring: an empty {type(scoring).__name__} gives no metric; scoring must be {MULTI_FORMS}")
+    fam = family_of(model_type)
+    if model_type in getattr(fam, "self_scored", ()):
+        raise ParamError(f"scoring {scoring!r} needs predictions; {model_type} only has score()")
+    for nm in names:
+        if not isinstance(nm, str) or nm in ("", "None"):
+            raise ParamError(f"scoring: every metric must be a scorer name, got {nm!r}; scoring must be {MULTI_FORMS}")
+        try:
+            scoring_mod.validate_scoring(nm, is_classifier(model_type))
+        except ValueError as e:
+            raise ParamError(str(e)) from None
+    if refit is True:
+        raise ParamError("For multi-metric scoring, the parameter refit must be set to a scorer key or False "
+                         f"(the scorer keys are {labels}); refit=True does not say which metric picks the best "
+                         "candidate")
+    if refit is False or refit is None:
+        return {"labels": labels, "names": names, "refit_metric": labels[0], "refit": False}
+    if not isinstance(refit, str) or refit not in labels:
+        raise ParamError(f"For multi-metric scoring, the parameter refit must be set to a scorer key or False; "
+                         f"{refit!r} is not one of the scorer keys {labels}")
+    return {"labels": labels, "names": names, "refit_metric": refit, "refit": True}
+
+
 def job_plan(request: Dict[str, Any]) -> Dict[str, Any]:
     """Derive everything a worker needs from a J1 request."""
     md = request.get("model_details") or {}
@@ -200,12 +256,21 @@ def job_plan(request: Dict[str, Any]) -> Dict[str, Any]:
         scoring = cvp.get("scoring")
         error_score = cvp.get("error_score", float("nan"))
         refit = cvp.get("refit", True)
+        multi = multimetric_options(scoring, refit, model_type)
     else:
         cands = [{}]
         cv = int(tp.get("cv", 5))   # the reference always runs cross_val_score(cv=5) (worker.py:326)
         scoring = tp.get("scoring")
         error_score = float("nan")
         refit = True
+        # a plain fit has one candidate and always refits it: train_params["refit"] only names
+        # the primary metric (default: the first label)
+        multi = multimetric_options(scoring, tp.get("refit") or False, model_type)
+        if multi is not None:
+            multi["refit"] = True
+    if multi is not None:   # the single-metric fields describe the primary metric
+        scoring = multi["names"][multi["labels"].index(multi["refit_metric"])]
+        refit = multi["refit"]
     if error_score is None:
         error_score = float("nan")
     par = str(tp.get("parallelism") or "auto")
@@ -234,6 +299,9 @@ def job_plan(request: Dict[str, Any]) -> Dict[str, Any]:
         plan["partial_dependence"] = pd_opts
     if staged is not None:
         plan["staged_scores"] = staged
+    if multi is not None:
+        plan["scoring_labels"], plan["scoring_names"] = multi["labels"], multi["names"]
+        plan["refit_metric"] = multi["refit_metric"]
     return plan
 
 
@@ -634,6 +702,9 @@ def run_slice(plan: Dict[str, Any], params: List[Dict[str, Any]], subtask_ids: L
                    error_score=plan["error_score"], keep_models="all" if keep_all else "none", seed=seed,
                    raise_batch_errors=True, permutation=plan.get("permutation_importance"),
                    partial_dependence=plan.get("partial_dependence"), staged=plan.get("staged_scores"))
+    if plan.get("scoring_labels"):   # multi-metric: (label, scorer) pairs and the primary label
+        spec.scoring = list(zip(plan["scoring_labels"], plan["scoring_names"]))
+        spec.refit_metric = plan["refit_metric"]
     received = utc_iso()
     slice_key = ",".join(str(int(c)) for c in cand_ids)
     gpu = dd.device.index if dd.is_gpu else None

@@ -87,6 +87,19 @@ def _prf(cm: torch.Tensor, avg: str, what: str) -> float:
     return float(v.mean())
 
 
+def _balanced(cm: torch.Tensor) -> float:
+    tp, tot = torch.diag(cm), cm.sum(1)
+    m = tot > 0
+    return float((tp[m] / tot[m]).mean())
+
+
+def _likelihood(name: str, cm: torch.Tensor) -> float:
+    tn, fp, fn, tp = (float(v) for v in cm.flatten())
+    if name == "positive_likelihood_ratio":   # sensitivity / (1 - specificity)
+        return (tp / (tp + fn)) / (fp / (fp + tn)) if fp > 0 and tp + fn > 0 else float("nan")
+    return -((fn / (tp + fn)) / (tn / (fp + tn))) if tn > 0 and tp + fn > 0 else float("nan")
+
+
 def _auc(y: torch.Tensor, s: torch.Tensor) -> float:
     y = y.double()
     order = torch.argsort(s.double())
@@ -191,6 +204,13 @@ def _cluster_score(name: str, y: torch.Tensor, p: torch.Tensor) -> float:
     _, pi = torch.unique(p.long(), return_inverse=True)
     R, K = int(yi.max()) + 1, int(pi.max()) + 1
     cont = torch.bincount(yi * K + pi, minlength=R * K).reshape(R, K).double()
+    return _cluster_from_cont(name, cont)
+
+
+def _cluster_from_cont(name: str, cont: torch.Tensor) -> float:
+    """``cont``: float64 contingency table over the labels that occur (no empty row or column) --
+    a confusion matrix without its empty rows and columns is the same table."""
+    R, K = int(cont.shape[0]), int(cont.shape[1])
     n = float(cont.sum())
     a, b = cont.sum(1), cont.sum(0)
     if name in ("rand_score", "adjusted_rand_score", "fowlkes_mallows_score"):
@@ -255,10 +275,7 @@ def score(name: str, y_true: torch.Tensor, pred: torch.Tensor, n_classes: int = 
     if name == "accuracy":
         return float((pred.long() == y_true.long()).double().mean())
     if name == "balanced_accuracy":
-        cm = _confusion(y_true, pred, n_classes)
-        tp, tot = torch.diag(cm), cm.sum(1)
-        m = tot > 0
-        return float((tp[m] / tot[m]).mean())
+        return _balanced(_confusion(y_true, pred, n_classes))
     for what in ("precision", "recall", "f1", "jaccard"):
         if name == what or name.startswith(what + "_"):
             avg = name.split("_", 1)[1] if "_" in name else "binary"
@@ -296,11 +313,7 @@ def score(name: str, y_true: torch.Tensor, pred: torch.Tensor, n_classes: int = 
     if name in ("positive_likelihood_ratio", "neg_negative_likelihood_ratio"):
         if n_classes != 2:
             raise ValueError(f"{name} needs a binary target")
-        cm = _confusion(y_true, pred, 2)
-        tn, fp, fn, tp = (float(v) for v in cm.flatten())
-        if name == "positive_likelihood_ratio":   # sensitivity / (1 - specificity)
-            return (tp / (tp + fn)) / (fp / (fp + tn)) if fp > 0 and tp + fn > 0 else float("nan")
-        return -((fn / (tp + fn)) / (tn / (fp + tn))) if tn > 0 and tp + fn > 0 else float("nan")
+        return _likelihood(name, _confusion(y_true, pred, 2))
     if name in _CLUSTER:
         return _cluster_score(name, y_true, pred)
     if name == "matthews_corrcoef":
@@ -358,3 +371,188 @@ def score(name: str, y_true: torch.Tensor, pred: torch.Tensor, n_classes: int = 
             return 1.0 if num == 0.0 else 0.0
         return 1.0 - num / den
     raise ValueError(f"unknown scorer {name!r}")
+
+
+# ---- scores from per-fit statistics (multi-metric jobs; docs/MULTIMETRIC.md) ---------------------
+# Every scorer below is a function of a fit's confusion matrix (classification) or of the 14 sums
+# of ``REG_SLOTS`` (regression): ``fit_statistics`` computes them for every fit of a batch in one
+# launch and one device->host read, and ``score_from_stats`` serves any number of metrics from it.
+_PRF = tuple(w + a for w in ("precision", "recall", "f1", "jaccard") for a in ("", "_macro", "_micro", "_weighted"))
+CLS_STAT_SCORERS = ("accuracy", "balanced_accuracy", *_PRF, "matthews_corrcoef", "positive_likelihood_ratio",
+                    "neg_negative_likelihood_ratio", *_CLUSTER)
+REG_STAT_SCORERS = ("r2", "neg_mean_squared_error", "neg_root_mean_squared_error", "neg_mean_absolute_error",
+                    "explained_variance", "max_error", "neg_max_error", "neg_mean_absolute_percentage_error",
+                    "neg_mean_squared_log_error", "neg_root_mean_squared_log_error", "neg_mean_poisson_deviance",
+                    "neg_mean_gamma_deviance")
+STAT_SCORERS = frozenset(CLS_STAT_SCORERS + REG_STAT_SCORERS)
+
+REG_SLOTS = 14
+WANT_LOG, WANT_POISSON, WANT_GAMMA = 1, 2, 4
+MAX_STAT_CLASSES = 64   # more classes: torch.bincount instead of the kernel / its host twin
+
+
+def stats_want(names) -> int:
+    """The ``want`` mask of the regression slots that cost a logarithm, for these scorers."""
+    want = 0
+    for nm in names:
+        if nm in ("neg_mean_squared_log_error", "neg_root_mean_squared_log_error"):
+            want |= WANT_LOG
+        elif nm == "neg_mean_poisson_deviance":
+            want |= WANT_POISSON
+        elif nm == "neg_mean_gamma_deviance":
+            want |= WANT_GAMMA
+    return want
+
+
+def _bincount_stats(rows, off, pred, y, C: int) -> torch.Tensor:
+    """The classification statistics by torch.bincount (more than ``MAX_STAT_CLASSES`` classes)."""
+    F = off.numel() - 1
+    CC = C * C
+    lens = off[1:] - off[:-1]
+    fit = torch.repeat_interleave(torch.arange(F, device=pred.device), lens.to(pred.device))
+    t, p = y.long()[rows.long()], pred.long()
+    ok = (t >= 0) & (t < C) & (p >= 0) & (p < C)
+    cell = torch.where(ok, t * C + p, torch.full_like(t, CC))
+    return torch.bincount(fit * (CC + 1) + cell, minlength=F * (CC + 1)).reshape(F, CC + 1)
+
+
+def fit_statistics(rows: torch.Tensor, fit_row_off, pred: torch.Tensor, y: torch.Tensor, n_classes: int = 0,
+                   want: int = 0) -> np.ndarray:
+    """Statistics of F fits whose held-out row ids (``rows``, int32) and predictions (``pred``)
+    lie concatenated, fit f owning ``[fit_row_off[f], fit_row_off[f + 1])``; ``y`` holds the
+    targets of the whole table (int32 class ids / float32 values) and is indexed by ``rows``.
+
+    ``n_classes`` >= 2: int64 [F, C, C] confusion matrices ``cm[t, p]`` (``pred`` int32 class ids);
+    a prediction or target outside [0, C) raises.  ``n_classes`` = 0: float64 [F, 14]
+    (``REG_SLOTS``; ``pred`` float32), the logarithm slots only as ``want`` asks.
+
+    csrc/kernels/score_stats.hip on the device of ``pred``, its host twin
+    (csrc/runtime/score_stats_cpu.cpp) for CPU tensors; one device->host read per call."""
+    from ..utils import native
+
+    off = np.ascontiguousarray(np.asarray(fit_row_off, dtype=np.int64))
+    F = int(off.size) - 1
+    C = int(n_classes)
+    reg = C == 0
+    if F < 0 or (not reg and C < 2):
+        raise ValueError("fit_statistics: fit_row_off needs F + 1 entries and n_classes 0 or >= 2")
+    total = int(pred.numel())
+    if F == 0:
+        return np.zeros((0, REG_SLOTS)) if reg else np.zeros((0, C, C), dtype=np.int64)
+    if off[0] != 0 or off[-1] != total or np.any(np.diff(off) < 0) or int(rows.numel()) != total:
+        raise ValueError("fit_statistics: fit_row_off must rise from 0 to the number of predictions and row ids")
+    if rows.dtype != torch.int32 or pred.dtype != (torch.float32 if reg else torch.int32) or \
+            y.dtype != (torch.float32 if reg else torch.int32):
+        raise ValueError("fit_statistics: rows int32; pred and y int32 (classification) or float32 (regression)")
+    dev = pred.device
+    if rows.device != dev or y.device != dev:
+        raise ValueError("fit_statistics: rows, pred and y must be on one device")
+    rows, pred, y = rows.contiguous(), pred.reshape(-1).contiguous(), y.contiguous()
+    max_rows = int(np.diff(off).max())
+    n = int(y.numel())
+    if not reg and C > MAX_STAT_CLASSES:
+        st = _bincount_stats(rows, torch.from_numpy(off), pred, y, C).cpu().numpy()
+    elif dev.type == "cuda":
+        lib = native.hip_lib()
+        if getattr(lib, "dml_fit_stats", None) is None:
+            raise RuntimeError("the HIP library has no dml_fit_stats: rebuild it")
+        tile = int(lib.dml_fit_stats_tile())
+        off_d = torch.from_numpy(off).to(dev)
+        gx = (max_rows + tile - 1) // tile
+        part = torch.empty(max(1, F * gx * REG_SLOTS), dtype=torch.float64, device=dev) if reg else None
+        out = torch.empty((F, REG_SLOTS), dtype=torch.float64, device=dev) if reg else \
+            torch.empty((F, C * C + 1), dtype=torch.int64, device=dev)
+        a = native.FitStatsArgs(rows=native.ptr(rows), fit_row_off=native.ptr(off_d), pred=native.ptr(pred),
+                                ycls=0 if reg else native.ptr(y), yreg=native.ptr(y) if reg else 0, n=n, C=C, F=F,
+                                max_rows=max_rows, want=int(want), part=native.ptr(part), out=native.ptr(out), f0=0)
+        with torch.cuda.device(dev):
+            rc = lib.dml_fit_stats(a, native.stream_handle(dev))
+        if rc != 0:
+            raise RuntimeError(f"dml_fit_stats failed (status {rc})")
+        st = out.cpu().numpy()   # the call's one device->host read
+    else:
+        lib = native.cpu_lib()
+        out = np.zeros((F, REG_SLOTS)) if reg else np.zeros((F, C * C + 1), dtype=np.int64)
+        rc = lib.dml_cpu_fit_stats(native.ptr(rows), native.ptr(off), native.ptr(pred), 0 if reg else native.ptr(y),
+                                   native.ptr(y) if reg else 0, n, C, F, max_rows, int(want), 0, native.ptr(out))
+        if rc != 0:
+            raise RuntimeError(f"dml_cpu_fit_stats failed (status {rc})")
+        st = out
+    lens = np.diff(off)
+    if reg:
+        if np.any(st[:, 0] != lens):
+            raise ValueError("fit_statistics: a row id lies outside the target vector")
+        return st
+    if np.any(st[:, C * C] != 0):
+        f = int(np.nonzero(st[:, C * C])[0][0])
+        raise ValueError(f"fit_statistics: fit {f} has {int(st[f, C * C])} prediction(s) or target(s) outside "
+                         f"[0, {C}) (or row ids outside the target vector)")
+    return np.ascontiguousarray(st[:, :C * C]).reshape(F, C, C)
+
+
+def score_from_stats(name: str, stats, n_classes: int = 2) -> float:
+    """``score(name, ...)`` of one fit from its ``fit_statistics`` entry: the int64 [C, C]
+    confusion matrix, or the float64 [14] sums.  The classification scorers run the helpers
+    ``score`` runs, on the same float64 matrix: the same bits."""
+    if name not in STAT_SCORERS:
+        raise ValueError(f"scorer {name!r} is not computable from fit statistics")
+    if name in CLS_STAT_SCORERS:
+        cm = torch.as_tensor(np.asarray(stats)).reshape(n_classes, n_classes).double()
+        n = float(cm.sum())
+        if n == 0:
+            return float("nan")
+        if name == "accuracy":
+            return float(torch.diag(cm).sum() / cm.sum())
+        if name == "balanced_accuracy":
+            return _balanced(cm)
+        for what in ("precision", "recall", "f1", "jaccard"):
+            if name == what or name.startswith(what + "_"):
+                avg = name.split("_", 1)[1] if "_" in name else "binary"
+                if avg == "binary" and n_classes != 2:
+                    raise ValueError(f"{name} needs a binary target; use {name}_macro")
+                return _prf(cm, avg, what)
+        if name in ("positive_likelihood_ratio", "neg_negative_likelihood_ratio"):
+            if n_classes != 2:
+                raise ValueError(f"{name} needs a binary target")
+            return _likelihood(name, cm)
+        if name in _CLUSTER:
+            return _cluster_from_cont(name, cm[cm.sum(1) > 0][:, cm.sum(0) > 0])
+        return _mcc(cm)
+    s = [float(v) for v in np.asarray(stats, dtype=np.float64).reshape(REG_SLOTS)]
+    n = s[0]
+    if n == 0:
+        return float("nan")
+    if name == "r2":
+        ss_tot = s[2] - s[1] * s[1] / n
+        if ss_tot <= 0.0:   # constant target
+            return 1.0 if s[4] == 0.0 else 0.0
+        return 1.0 - s[4] / ss_tot
+    if name == "neg_mean_squared_error":
+        return -(s[4] / n)
+    if name == "neg_root_mean_squared_error":
+        return -math.sqrt(s[4] / n)
+    if name == "neg_mean_absolute_error":
+        return -(s[5] / n)
+    if name in ("max_error", "neg_max_error"):
+        return -s[6]
+    if name == "explained_variance":
+        ve = max(s[4] / n - (s[3] / n) ** 2, 0.0)
+        vt = s[2] / n - (s[1] / n) ** 2
+        return 1.0 - ve / vt if vt > 0 else (1.0 if ve == 0 else 0.0)
+    if name == "neg_mean_absolute_percentage_error":
+        return -(s[7] / n)
+    if name in ("neg_mean_squared_log_error", "neg_root_mean_squared_log_error"):
+        if s[9] != 0:
+            raise ValueError("Mean Squared Logarithmic Error cannot be used when targets contain values less "
+                             "than or equal to -1.")
+        msle = s[8] / n
+        return -msle if name == "neg_mean_squared_log_error" else -math.sqrt(msle)
+    if name == "neg_mean_poisson_deviance":
+        if s[11] != 0:
+            raise ValueError("Mean Tweedie deviance error with power=1 can only be used on non-negative y and "
+                             "strictly positive y_pred.")
+        return -(s[10] / n)
+    if s[13] != 0:   # neg_mean_gamma_deviance
+        raise ValueError("Mean Tweedie deviance error with power=2 can only be used on strictly positive y "
+                         "and y_pred.")
+    return -(s[12] / n)

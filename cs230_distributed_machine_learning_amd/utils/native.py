@@ -134,6 +134,11 @@ GbStatsArgs = _i64_struct(
     ["n", "K", "A", "raw", "ycls", "yreg", "roles", "inbag", "val", "fit_raw", "fit_loss", "fit_role", "fit_inbag",
      "fit_val", "fit_out", "fit_dpos", "fit_alpha", "delta", "part", "stats", "stage", "n_stages"],
 )
+# csrc/kernels/score_stats.hip FitStatsArgs (per-fit confusion matrices / regression sums)
+FitStatsArgs = _i64_struct(
+    "FitStatsArgs",
+    ["rows", "fit_row_off", "pred", "ycls", "yreg", "n", "C", "F", "max_rows", "want", "part", "out", "f0"],
+)
 # csrc/kernels/forest_mae.hip (criterion="absolute_error" builder)
 MaeArgs = _i64_struct(
     "MaeArgs",
@@ -186,6 +191,9 @@ def cpu_lib() -> ctypes.CDLL:
             lib.dml_cpu_bin.argtypes = [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64]
             lib.dml_cpu_gbrt_stage_stats.restype = None
             lib.dml_cpu_gbrt_stage_stats.argtypes = [c_i64, c_i64, c_i64] + [c_vp] * 17 + [c_i64, c_i64]
+            lib.dml_cpu_fit_stats_tile.restype = c_i32
+            lib.dml_cpu_fit_stats.restype = c_i32
+            lib.dml_cpu_fit_stats.argtypes = [c_vp] * 5 + [c_i64] * 5 + [c_vp, c_vp]
             lib.dml_cpu_svm_sizeof_prob.restype = c_i32
             lib.dml_cpu_svm_smo.argtypes = [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]
             lib.dml_cpu_svm_platt_fit.restype = c_i32
@@ -301,6 +309,11 @@ def _register_optional(lib) -> None:
         "dml_gb_fit_sel_step": (c_i32, [ctypes.POINTER(GbGradArgs), c_i32, c_i32, c_vp]),
         "dml_gb_sizeof_stats_args": (c_i32, []),
         "dml_gb_stage_stats": (c_i32, [ctypes.POINTER(GbStatsArgs), c_vp]),
+        "dml_fit_stats_sizeof_args": (c_i32, []),
+        "dml_fit_stats_tile": (c_i32, []),
+        "dml_fit_stats_small_c": (c_i32, []),
+        "dml_fit_stats_max_c": (c_i32, []),
+        "dml_fit_stats": (c_i32, [ctypes.POINTER(FitStatsArgs), c_vp]),
         "dml_exp_hist": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
         "dml_forest_release_scratch": (c_i32, []),
         "dml_forest_block_stash_planes": (c_i32, []),
@@ -323,6 +336,9 @@ def _register_optional(lib) -> None:
     if (getattr(lib, "dml_gb_sizeof_stats_args", None) is not None
             and lib.dml_gb_sizeof_stats_args() != ctypes.sizeof(GbStatsArgs)):
         raise RuntimeError("GBRT stage statistics argument layout mismatch between HIP library and Python")
+    if (getattr(lib, "dml_fit_stats_sizeof_args", None) is not None
+            and lib.dml_fit_stats_sizeof_args() != ctypes.sizeof(FitStatsArgs)):
+        raise RuntimeError("FitStatsArgs layout mismatch between HIP library and Python")
     if getattr(lib, "dml_mae_sizeof_args", None) is not None and lib.dml_mae_sizeof_args() != ctypes.sizeof(MaeArgs):
         raise RuntimeError("MAE builder argument layout mismatch between HIP library and Python")
     if getattr(lib, "dml_lr_sizeof_fwd_args", None) is not None:
