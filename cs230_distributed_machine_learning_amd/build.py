@@ -191,6 +191,27 @@ def build_sanitized(force: bool = False) -> str:
     return SAN_EXE
 
 
+RANK_SAN_EXE = os.path.join(LIB, "rank_stats_selftest_asan")
+
+
+def build_rank_selftest(force: bool = False) -> str:
+    """``csrc/runtime/rank_stats_cpu.cpp`` + ``csrc/tests/rank_stats_selftest.cpp`` with
+    AddressSanitizer and UndefinedBehaviorSanitizer, as ``build_sanitized``: a stand-alone
+    executable; any report aborts it."""
+    srcs = [os.path.join(CSRC, "runtime", "rank_stats_cpu.cpp"), os.path.join(CSRC, "tests", "rank_stats_selftest.cpp")]
+    os.makedirs(LIB, exist_ok=True)
+    cxx = os.environ.get("CXX", shutil.which("g++") or "c++")
+    flags = [cxx, "-O1", "-g", "-std=c++17", "-fopenmp", "-ffp-contract=off", "-fsanitize=address,undefined",
+             "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
+    with _BuildLock():
+        if force or _stale_by_hash(RANK_SAN_EXE, srcs, flags):
+            tmp = _tmp(RANK_SAN_EXE)
+            _run([*flags, *srcs, "-o", tmp])
+            os.replace(tmp, RANK_SAN_EXE)
+            _stamp(RANK_SAN_EXE, srcs, flags)
+    return RANK_SAN_EXE
+
+
 def build_all(force: bool = False) -> tuple[str, str]:
     return build_cpu(force), build_hip(force)
 
@@ -208,6 +229,7 @@ if __name__ == "__main__":
         sys.exit(0)
     if args.sanitize:
         print(build_sanitized(args.force))
+        print(build_rank_selftest(args.force))
     print(build_cpu(args.force))
     if not args.cpu_only:
         print(build_hip(args.force))

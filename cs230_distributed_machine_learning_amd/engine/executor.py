@@ -113,7 +113,14 @@ def _batched_scores(data, tasks, outputs: Dict[int, FitOutput], scorer: str) -> 
     grouped by split (same held-out rows), their predictions stacked and scored together --
     instead of one reduction and one host sync per fit (a 2,560-fit LogisticRegression batch
     spent 0.27 s per search in per-fit syncs).  Exact: a mean of 0/1 counts is the same
-    double whatever the reduction order (so only accuracy is batched here)."""
+    double whatever the reduction order.  roc_auc, roc_auc_ovr and roc_auc_ovr_weighted are
+    batched too (``_rank_proba_scores``): their statistics are integers.  Every other scorer is
+    a floating-point sum whose last place would move, and stays per fit."""
+    if scorer in _EXACT_RANK and getattr(data, "is_gpu", False):
+        # roc_auc*: one division of exact integer rank statistics, done as torch does it for device
+        # tensors (score_from_rank_stats device_division): the bits of scoring._auc on this data
+        # path (docs/RANK_SCORES.md); fits that are not batched are scored per fit as before
+        return {tid: v[scorer] for tid, v in _rank_proba_scores(data, tasks, outputs, [scorer], True).items()}
     if scorer != "accuracy" or not getattr(data, "is_gpu", False):
         return {}
     by_split: Dict[int, List[FitTask]] = {}
@@ -135,6 +142,78 @@ def _batched_scores(data, tasks, outputs: Dict[int, FitOutput], scorer: str) -> 
     return dict(zip(ids, torch.cat(vals).cpu().tolist()))
 
 
+_EXACT_RANK = ("roc_auc", "roc_auc_ovr", "roc_auc_ovr_weighted")
+
+
+def _rank_proba_scores(data, tasks, outputs: Dict[int, FitOutput], names,
+                       device_division: bool = False) -> Dict[int, Dict[str, float]]:
+    """The ranking and probability scorers among ``names`` (``scoring.RANK_SCORERS``,
+    ``scoring.PROBA_SUM_SCORERS``) for every fit that hands over float32 scores on the targets'
+    device: {task_id: {scorer name: score}}.  The binary column (``proba[:, 1]``, or the decision
+    values when there are no probabilities) of those fits is concatenated once and
+    ``scoring.rank_statistics`` runs once on it; the whole probability matrices are concatenated
+    once for one ``rank_statistics`` call (roc_auc_ovr*) and one ``proba_statistics`` call.  A fit
+    that is absent from the result -- float64 scores (SVC), another length or device, more classes
+    than the kernels take, a row-sharded table -- is scored by ``scoring.score`` as before."""
+    names = [nm for nm in dict.fromkeys(names) if nm in scoring_mod.RANK_SCORERS or nm in scoring_mod.PROBA_SUM_SCORERS]
+    C = int(getattr(data, "n_classes", 0) or 0)
+    if not names or C < 2 or getattr(data, "is_row_shard", False):
+        return {}
+    y_all = data.y_cls
+    col_names = [nm for nm in names if nm in ("roc_auc", "average_precision")] if C == 2 else []
+    ovr_names = [nm for nm in names if nm.startswith("roc_auc_ovr")]
+    sum_names = [nm for nm in names if nm in scoring_mod.PROBA_SUM_SCORERS]
+    if C > scoring_mod.MAX_STAT_CLASSES:
+        ovr_names, sum_names = [], []
+
+    def f32(v, shape):
+        return isinstance(v, torch.Tensor) and v.dtype == torch.float32 and v.device == y_all.device and \
+            tuple(v.shape) == shape
+
+    col, mat = [], []
+    for t in tasks:
+        o = outputs.get(t.task_id)
+        m = int(data.test_rows[t.split].numel())
+        if o is None or o.error or m == 0:
+            continue
+        if f32(o.proba, (m, C)):
+            mat.append((t, o.proba))
+            col.append((t, o.proba[:, 1]))
+        elif o.proba is None and f32(o.decision, (m,)):
+            col.append((t, o.decision))
+    res: Dict[int, Dict[str, float]] = {}
+
+    def cat(group):
+        rows = torch.cat([data.test_rows[t.split] for t, _s in group])
+        off = np.concatenate([[0], np.cumsum([int(s.shape[0]) for _t, s in group])]).astype(np.int64)
+        return rows, off, torch.cat([s for _t, s in group])
+
+    try:
+        if col and col_names:
+            rows, off, s = cat(col)
+            st = scoring_mod.rank_statistics(rows, off, s, y_all, C, pos0=1, want=scoring_mod.rank_want(col_names))
+            for i, (t, _s) in enumerate(col):
+                res.setdefault(t.task_id, {}).update(
+                    {nm: scoring_mod.score_from_rank_stats(nm, st[i], C, device_division) for nm in col_names})
+        if mat and (ovr_names or sum_names):
+            rows, off, P = cat(mat)
+            if ovr_names:
+                st = scoring_mod.rank_statistics(rows, off, P, y_all, C, pos0=0)
+                for i, (t, _s) in enumerate(mat):
+                    res.setdefault(t.task_id, {}).update(
+                        {nm: scoring_mod.score_from_rank_stats(nm, st[i], C, device_division) for nm in ovr_names})
+            if sum_names:
+                ps = scoring_mod.proba_statistics(rows, off, P, y_all, C, want=scoring_mod.proba_want(sum_names))
+                for i, (t, _s) in enumerate(mat):
+                    res.setdefault(t.task_id, {}).update(
+                        {nm: scoring_mod.score_from_rank_stats(nm, ps[i], C) for nm in sum_names})
+    except ValueError:
+        # entries the statistics refuse (a NaN score, a target outside the classes): the per-fit
+        # scorers keep their behaviour on such data
+        return {}
+    return res
+
+
 def _scores_for(data, task: FitTask, out: FitOutput, scorer: str, pre: Optional[Dict[int, float]] = None):
     if pre is not None and task.task_id in pre:
         return pre[task.task_id]
@@ -148,8 +227,9 @@ def _multi_scores(data, tasks, outputs: Dict[int, FitOutput], pairs, clf: bool) 
     """Every metric of a multi-metric job for every successful fit, CV and holdout together:
     {task_id: {label: score}}.  The predictions of the whole family batch are stacked and
     ``scoring.fit_statistics`` runs once (one launch, one device->host read); every metric in
-    ``scoring.STAT_SCORERS`` is derived from that read-back.  The probability, ranking and median
-    scorers go through ``scoring.score`` per fit, as in a single-metric job -- and so does a fit
+    ``scoring.STAT_SCORERS`` is derived from that read-back, and the ranking and probability
+    scorers from the batched rank and probability statistics (``_rank_proba_scores``).  The median
+    scorers and roc_auc_ovo* go through ``scoring.score`` per fit, as in a single-metric job -- and so does a fit
     whose predictions are not the kernel's types (float64 regression predictions are scored in
     float64, not rounded to float32), and every fit of a row-sharded table (its resident targets
     are one rank's)."""
@@ -177,6 +257,7 @@ def _multi_scores(data, tasks, outputs: Dict[int, FitOutput], pairs, clf: bool) 
         off = np.concatenate([[0], np.cumsum([p.numel() for p in preds])]).astype(np.int64)
         st = scoring_mod.fit_statistics(rows, off, pred, y_all, C, want=scoring_mod.stats_want(stat_names))
         stats = {t.task_id: st[i] for i, t in enumerate(batched)}
+    ranked = _rank_proba_scores(data, live, outputs, [nm for _l, nm in pairs]) if clf else {}
     res: Dict[int, Dict[str, float]] = {}
     for t in live:
         o = outputs[t.task_id]
@@ -185,6 +266,8 @@ def _multi_scores(data, tasks, outputs: Dict[int, FitOutput], pairs, clf: bool) 
         for label, nm in pairs:
             if nm in scoring_mod.STAT_SCORERS and t.task_id in stats:
                 vals[label] = scoring_mod.score_from_stats(nm, stats[t.task_id], data.n_classes)
+            elif nm in ranked.get(t.task_id, ()):
+                vals[label] = ranked[t.task_id][nm]
             else:
                 if y is None:
                     y = data.test_targets(t.split)

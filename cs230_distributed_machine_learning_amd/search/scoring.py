@@ -556,3 +556,263 @@ def score_from_stats(name: str, stats, n_classes: int = 2) -> float:
         raise ValueError("Mean Tweedie deviance error with power=2 can only be used on strictly positive y "
                          "and y_pred.")
     return -(s[12] / n)
+
+
+# ---- rank and probability statistics (multi-metric jobs, single-metric roc_auc; docs/RANK_SCORES.md) ----
+# A *problem* is one (fit, score column).  ``rank_statistics`` sorts every problem's negative and
+# positive scores on the device (one segmented radix sort for the whole batch) and reduces them to
+# n_neg, n_pos, the integer U2 = sum over positives of (2 #{smaller negatives} + #{equal negatives})
+# and the average precision; ``proba_statistics`` reduces the probabilities of every fit to the sums
+# of the log loss, the Brier score and the top-2 hits.  One device->host read per call each.
+RANK_SCORERS = ("roc_auc", "average_precision", "roc_auc_ovr", "roc_auc_ovr_weighted")
+PROBA_SUM_SCORERS = ("neg_log_loss", "neg_brier_score", "top_k_accuracy")
+WANT_AP = 1
+WANT_LOG_LOSS, WANT_BRIER, WANT_TOP2 = 1, 2, 4
+RANK_DTYPE = np.dtype([("n_neg", "<i8"), ("n_pos", "<i8"), ("u2", "<u8"), ("ap", "<f8")])
+PROBA_DTYPE = np.dtype([("n", "<i8"), ("log", "<f8"), ("brier", "<f8"), ("top2", "<i8"), ("bad", "<i8")])
+# fits are sorted in chunks of at most this many keys (two uint32 buffers: 2 GiB), a longer fit alone
+RANK_CHUNK_KEYS = 1 << 28
+
+
+def rank_want(names) -> int:
+    return WANT_AP if "average_precision" in names else 0
+
+
+def proba_want(names) -> int:
+    return ((WANT_LOG_LOSS if "neg_log_loss" in names else 0) | (WANT_BRIER if "neg_brier_score" in names else 0)
+            | (WANT_TOP2 if "top_k_accuracy" in names else 0))
+
+
+def _stat_inputs(who: str, rows, fit_row_off, score, y, n_classes: int, K: int):
+    """The host-side checks ``rank_statistics`` and ``proba_statistics`` share."""
+    off = np.ascontiguousarray(np.asarray(fit_row_off, dtype=np.int64))
+    F = int(off.size) - 1
+    if F < 0 or int(n_classes) < 2 or K < 1:
+        raise ValueError(f"{who}: fit_row_off needs F + 1 entries, n_classes >= 2 and at least one score column")
+    total = int(rows.numel())
+    if F and (off[0] != 0 or off[-1] != total or np.any(np.diff(off) < 0)) or int(score.numel()) != total * K:
+        raise ValueError(f"{who}: fit_row_off must rise from 0 to the number of row ids, with {K} score(s) each")
+    if rows.dtype != torch.int32 or score.dtype != torch.float32 or y.dtype != torch.int32:
+        raise ValueError(f"{who}: rows and y int32, score float32")
+    if rows.device != score.device or y.device != score.device:
+        raise ValueError(f"{who}: rows, score and y must be on one device")
+    return off, F, rows.contiguous(), score.reshape(-1).contiguous(), y.contiguous()
+
+
+def _raise_bad(who: str, bad) -> None:
+    if np.any(bad != 0):
+        f = int(np.nonzero(bad)[0][0])
+        raise ValueError(f"{who}: fit {f} has {int(bad[f])} entr(ies) that cannot be scored: a NaN score, a target "
+                         f"outside the classes or a row id outside the target vector")
+
+
+def _fit_chunks(off: np.ndarray, K: int, cap: int):
+    """[c0, c1) ranges of fits holding at most ``cap`` keys each (a longer fit is a chunk of its own)."""
+    F = off.size - 1
+    c0 = 0
+    while c0 < F:
+        c1 = c0 + 1
+        while c1 < F and (off[c1 + 1] - off[c0]) * K <= cap:
+            c1 += 1
+        yield c0, c1
+        c0 = c1
+
+
+def rank_statistics(rows: torch.Tensor, fit_row_off, score: torch.Tensor, y: torch.Tensor, n_classes: int,
+                    pos0: int = 1, want: int = 0, timings: Optional[dict] = None) -> np.ndarray:
+    """Rank statistics of F fits whose held-out row ids (``rows``, int32) and scores (``score``,
+    float32 [total] or [total, K]) lie concatenated, fit f owning ``[fit_row_off[f],
+    fit_row_off[f + 1])``; ``y`` holds the int32 class ids of the whole table.  Column j is scored
+    with positive class ``pos0 + j``.  Returns a ``RANK_DTYPE`` record array [F, K]; ``ap`` only
+    with ``WANT_AP``.  A NaN score, a target outside [0, n_classes) or a row id outside ``y``
+    raises and names the fit.  With ``timings`` (a dict; the device only) the partition, the sort and
+    the reduce are launched as three calls with device events between them, and the dict receives
+    ``partition_ms``, ``sort_ms`` and ``reduce_ms``.
+
+    csrc/kernels/rank_stats.hip on the device of ``score``, its host twin
+    (csrc/runtime/rank_stats_cpu.cpp) for CPU tensors; one device->host read per call."""
+    from ..utils import native
+
+    K = int(score.shape[1]) if score.dim() == 2 else 1
+    off, F, rows, score, y = _stat_inputs("rank_statistics", rows, fit_row_off, score, y, n_classes, K)
+    C, n = int(n_classes), int(y.numel())
+    if F == 0:
+        return np.zeros((0, K), dtype=RANK_DTYPE)
+    dev = score.device
+    if dev.type == "cuda":
+        lib = native.hip_lib()
+        if getattr(lib, "dml_rank_stats", None) is None:
+            raise RuntimeError("the HIP library has no dml_rank_stats: rebuild it")
+        tile = int(lib.dml_rank_stats_tile())
+        raw = torch.empty(F * K * 4 + F, dtype=torch.int64, device=dev)   # the statistics, then bad [F]
+        chunks = list(_fit_chunks(off, K, RANK_CHUNK_KEYS))
+        n_keys = max(int(off[c1] - off[c0]) * K for c0, c1 in chunks)
+        longest = int(np.diff(off).max())
+        hist_b = max(int(lib.dml_seg_sort_hist_bytes(2 * max(c1 - c0 for c0, c1 in chunks) * K, longest)), 4)
+        keys = torch.empty(max(1, n_keys), dtype=torch.int32, device=dev)
+        tmp = torch.empty(max(1, n_keys), dtype=torch.int32, device=dev)
+        hist = torch.empty(hist_b // 4, dtype=torch.int32, device=dev)
+        gx = (longest + tile - 1) // tile
+        part = torch.empty(max(1, max(c1 - c0 for c0, c1 in chunks) * K * gx), dtype=torch.float64, device=dev)
+        events = []
+        with torch.cuda.device(dev):
+            for c0, c1 in chunks:
+                off_d = torch.from_numpy(off[c0:c1 + 1] - off[c0]).to(dev)
+                e0 = int(off[c0])
+                a = native.RankStatsArgs(
+                    rows=native.ptr(rows) + 4 * e0, fit_row_off=native.ptr(off_d), score=native.ptr(score) + 4 * e0 * K,
+                    ycls=native.ptr(y), n=n, C=C, K=K, pos0=int(pos0), F=c1 - c0,
+                    max_rows=int(np.diff(off[c0:c1 + 1]).max()), want=int(want), keys=native.ptr(keys),
+                    tmp=native.ptr(tmp), hist=native.ptr(hist), part=native.ptr(part),
+                    out=native.ptr(raw) + 8 * c0 * K * 4, bad=native.ptr(raw) + 8 * (F * K * 4 + c0), phase=0, f0=0)
+                for phase in ((0,) if timings is None else (1, 2, 3)):
+                    a.phase = phase
+                    events.append(torch.cuda.Event(enable_timing=True))
+                    events[-1].record()
+                    rc = lib.dml_rank_stats(a, native.stream_handle(dev))
+                    if rc != 0:
+                        raise RuntimeError(f"dml_rank_stats failed (status {rc})")
+            events.append(torch.cuda.Event(enable_timing=True))
+            events[-1].record()
+        st = raw.cpu().numpy()   # the call's one device->host read
+        if timings is not None:
+            for q, key in enumerate(("partition_ms", "sort_ms", "reduce_ms")):
+                timings[key] = sum(events[i].elapsed_time(events[i + 1]) for i in range(q, len(events) - 1, 3))
+    else:
+        lib = native.cpu_lib()
+        st = np.zeros(F * K * 4 + F, dtype=np.int64)
+        rc = lib.dml_cpu_rank_stats(native.ptr(rows), native.ptr(off), native.ptr(score), native.ptr(y), n, C, K,
+                                    int(pos0), F, int(np.diff(off).max()), int(want), native.ptr(st),
+                                    native.ptr(st) + 8 * F * K * 4)
+        if rc != 0:
+            raise RuntimeError(f"dml_cpu_rank_stats failed (status {rc})")
+    _raise_bad("rank_statistics", st[F * K * 4:])
+    return np.ascontiguousarray(st[:F * K * 4]).view(RANK_DTYPE).reshape(F, K)
+
+
+def proba_statistics(rows: torch.Tensor, fit_row_off, proba: torch.Tensor, y: torch.Tensor, n_classes: int,
+                     want: int = 0) -> np.ndarray:
+    """Probability sums of F fits, inputs as ``rank_statistics`` with ``proba`` float32
+    [total, C], C = ``n_classes`` <= ``MAX_STAT_CLASSES``.  Returns a ``PROBA_DTYPE`` record array
+    [F]: ``n``, ``log`` = sum log(clamp(p[y], eps, 1 - eps)), ``brier`` (binary: the positive class's
+    squared error; otherwise summed over the classes) and ``top2`` (rows where fewer than two
+    classes rank ahead of the target; ties: the higher class index first), each as ``want`` asks."""
+    from ..utils import native
+
+    C = int(n_classes)
+    if proba.dim() != 2 or int(proba.shape[1]) != C or C > MAX_STAT_CLASSES:
+        raise ValueError(f"proba_statistics: proba must be [total, n_classes] with at most {MAX_STAT_CLASSES} classes")
+    off, F, rows, proba, y = _stat_inputs("proba_statistics", rows, fit_row_off, proba, y, C, C)
+    n = int(y.numel())
+    if F == 0:
+        return np.zeros(0, dtype=PROBA_DTYPE)
+    max_rows = int(np.diff(off).max())
+    dev = proba.device
+    if dev.type == "cuda":
+        lib = native.hip_lib()
+        if getattr(lib, "dml_proba_stats", None) is None:
+            raise RuntimeError("the HIP library has no dml_proba_stats: rebuild it")
+        tile = int(lib.dml_rank_stats_tile())
+        gx = (max_rows + tile - 1) // tile
+        off_d = torch.from_numpy(off).to(dev)
+        part = torch.empty(max(1, F * gx * 2), dtype=torch.float64, device=dev)
+        raw = torch.empty(F * 5, dtype=torch.int64, device=dev)
+        a = native.RankStatsArgs(rows=native.ptr(rows), fit_row_off=native.ptr(off_d), score=native.ptr(proba),
+                                 ycls=native.ptr(y), n=n, C=C, K=C, pos0=0, F=F, max_rows=max_rows, want=int(want),
+                                 keys=0, tmp=0, hist=0, part=native.ptr(part), out=native.ptr(raw), bad=0, phase=0, f0=0)
+        with torch.cuda.device(dev):
+            rc = lib.dml_proba_stats(a, native.stream_handle(dev))
+        if rc != 0:
+            raise RuntimeError(f"dml_proba_stats failed (status {rc})")
+        st = raw.cpu().numpy()   # the call's one device->host read
+    else:
+        lib = native.cpu_lib()
+        st = np.zeros(F * 5, dtype=np.int64)
+        rc = lib.dml_cpu_proba_stats(native.ptr(rows), native.ptr(off), native.ptr(proba), native.ptr(y), n, C, F,
+                                     max_rows, int(want), native.ptr(st))
+        if rc != 0:
+            raise RuntimeError(f"dml_cpu_proba_stats failed (status {rc})")
+    st = st.view(PROBA_DTYPE).reshape(F)
+    _raise_bad("proba_statistics", st["bad"])
+    return st
+
+
+def segmented_sort_u32(keys: torch.Tensor, seg_off) -> torch.Tensor:
+    """``keys`` (int32 or uint32, read as unsigned 32-bit) with every segment ``[seg_off[s],
+    seg_off[s + 1])`` sorted ascending: the radix sort of csrc/kernels/rank_stats.hip on the device
+    of ``keys``, ``std::sort`` per segment on the host.  Keys outside every segment are unchanged."""
+    from ..utils import native
+
+    off = np.ascontiguousarray(np.asarray(seg_off, dtype=np.int64))
+    S = int(off.size) - 1
+    if keys.dtype not in (torch.int32, torch.uint32) or keys.dim() != 1:
+        raise ValueError("segmented_sort_u32: keys must be a 1-d int32 or uint32 tensor")
+    if S < 0 or (S and (off[0] < 0 or off[-1] > keys.numel() or np.any(np.diff(off) < 0))):
+        raise ValueError("segmented_sort_u32: seg_off must rise within the keys")
+    out = keys.contiguous().clone()
+    if S == 0 or int(np.diff(off).max()) == 0:
+        return out
+    max_len = int(np.diff(off).max())
+    if out.device.type == "cuda":
+        lib = native.hip_lib()
+        if getattr(lib, "dml_seg_sort_u32", None) is None:
+            raise RuntimeError("the HIP library has no dml_seg_sort_u32: rebuild it")
+        dev = out.device
+        off_d = torch.from_numpy(off).to(dev)
+        tmp = torch.empty_like(out)
+        hist = torch.empty(int(lib.dml_seg_sort_hist_bytes(S, max_len)) // 4, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            rc = lib.dml_seg_sort_u32(native.ptr(out), native.ptr(off_d), S, max_len, native.ptr(tmp), native.ptr(hist),
+                                      native.stream_handle(dev))
+            torch.cuda.synchronize(dev)   # tmp and hist stay alive until the sort has run
+    else:
+        rc = native.cpu_lib().dml_cpu_seg_sort_u32(native.ptr(out), native.ptr(off), S)
+    if rc != 0:
+        raise RuntimeError(f"segmented_sort_u32 failed (status {rc})")
+    return out
+
+
+def _auc_from_rank(rec, device_division: bool = False) -> float:
+    n_pos, n_neg = int(rec["n_pos"]), int(rec["n_neg"])
+    if n_pos == 0 or n_neg == 0:
+        return float("nan")
+    if device_division:   # a device tensor over a host scalar: torch multiplies by the scalar's reciprocal
+        return (int(rec["u2"]) * 0.5) * (1.0 / (float(n_pos) * float(n_neg)))
+    return (int(rec["u2"]) * 0.5) / (float(n_pos) * float(n_neg))
+
+
+def score_from_rank_stats(name: str, stats, n_classes: int = 2, device_division: bool = False) -> float:
+    """``score(name, ...)`` of one fit from its ``rank_statistics`` entry (``RANK_SCORERS``: the
+    records of its K columns; the binary scorers read the last one) or its ``proba_statistics``
+    entry (``PROBA_SUM_SCORERS``).  The AUCs are one division of exact integers: the bits of
+    ``score`` on host tensors.  On device tensors ``score`` divides by multiplying with the
+    reciprocal of the host scalar ``n_pos * n_neg``, which can round the last place differently;
+    ``device_division`` reproduces that, so a single-metric job on the GPU data path keeps its
+    bits.  The sums differ from ``score``'s in the last places (docs/RANK_SCORES.md)."""
+    if name in RANK_SCORERS:
+        st = np.asarray(stats).reshape(-1)
+        if name in ("roc_auc", "average_precision"):
+            if n_classes != 2:
+                raise ValueError(f"{name} needs probabilities or decision values of a binary classifier")
+            rec = st[-1]
+            if int(rec["n_pos"]) + int(rec["n_neg"]) == 0:
+                return float("nan")
+            if name == "roc_auc":
+                return _auc_from_rank(rec, device_division)
+            return float(rec["ap"]) if int(rec["n_pos"]) else float("nan")
+        if int(st[0]["n_pos"]) + int(st[0]["n_neg"]) == 0:
+            return float("nan")
+        # the expressions of _multiclass_auc on the per-class AUCs and prevalences: the same bits
+        aucs = torch.tensor([_auc_from_rank(r, device_division) for r in st], dtype=torch.float64)
+        prev = torch.tensor([int(r["n_pos"]) for r in st], dtype=torch.int64).double()
+        return float((aucs * prev).sum() / prev.sum()) if name.endswith("_weighted") else float(aucs.mean())
+    if name not in PROBA_SUM_SCORERS:
+        raise ValueError(f"scorer {name!r} is not computable from rank or probability statistics")
+    n = int(stats["n"])
+    if n == 0:
+        return float("nan")
+    if name == "neg_log_loss":
+        return float(stats["log"]) / n
+    if name == "neg_brier_score":
+        return -(float(stats["brier"]) / n)
+    return 1.0 if n_classes <= 2 else int(stats["top2"]) / n

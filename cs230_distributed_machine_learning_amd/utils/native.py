@@ -139,6 +139,12 @@ FitStatsArgs = _i64_struct(
     "FitStatsArgs",
     ["rows", "fit_row_off", "pred", "ycls", "yreg", "n", "C", "F", "max_rows", "want", "part", "out", "f0"],
 )
+# csrc/kernels/rank_stats.hip RankStatsArgs (per-problem rank statistics / per-fit probability sums)
+RankStatsArgs = _i64_struct(
+    "RankStatsArgs",
+    ["rows", "fit_row_off", "score", "ycls", "n", "C", "K", "pos0", "F", "max_rows", "want", "keys", "tmp", "hist",
+     "part", "out", "bad", "phase", "f0"],
+)
 # csrc/kernels/forest_mae.hip (criterion="absolute_error" builder)
 MaeArgs = _i64_struct(
     "MaeArgs",
@@ -194,6 +200,13 @@ def cpu_lib() -> ctypes.CDLL:
             lib.dml_cpu_fit_stats_tile.restype = c_i32
             lib.dml_cpu_fit_stats.restype = c_i32
             lib.dml_cpu_fit_stats.argtypes = [c_vp] * 5 + [c_i64] * 5 + [c_vp, c_vp]
+            lib.dml_cpu_rank_stats_tile.restype = c_i32
+            lib.dml_cpu_seg_sort_u32.restype = c_i32
+            lib.dml_cpu_seg_sort_u32.argtypes = [c_vp, c_vp, c_i64]
+            lib.dml_cpu_rank_stats.restype = c_i32
+            lib.dml_cpu_rank_stats.argtypes = [c_vp] * 4 + [c_i64] * 7 + [c_vp, c_vp]
+            lib.dml_cpu_proba_stats.restype = c_i32
+            lib.dml_cpu_proba_stats.argtypes = [c_vp] * 4 + [c_i64] * 5 + [c_vp]
             lib.dml_cpu_svm_sizeof_prob.restype = c_i32
             lib.dml_cpu_svm_smo.argtypes = [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]
             lib.dml_cpu_svm_platt_fit.restype = c_i32
@@ -314,6 +327,13 @@ def _register_optional(lib) -> None:
         "dml_fit_stats_small_c": (c_i32, []),
         "dml_fit_stats_max_c": (c_i32, []),
         "dml_fit_stats": (c_i32, [ctypes.POINTER(FitStatsArgs), c_vp]),
+        "dml_rank_stats_sizeof_args": (c_i32, []),
+        "dml_rank_stats_tile": (c_i32, []),
+        "dml_rank_stats_max_c": (c_i32, []),
+        "dml_seg_sort_hist_bytes": (c_i64, [c_i64, c_i64]),
+        "dml_seg_sort_u32": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
+        "dml_rank_stats": (c_i32, [ctypes.POINTER(RankStatsArgs), c_vp]),
+        "dml_proba_stats": (c_i32, [ctypes.POINTER(RankStatsArgs), c_vp]),
         "dml_exp_hist": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
         "dml_forest_release_scratch": (c_i32, []),
         "dml_forest_block_stash_planes": (c_i32, []),
@@ -339,6 +359,9 @@ def _register_optional(lib) -> None:
     if (getattr(lib, "dml_fit_stats_sizeof_args", None) is not None
             and lib.dml_fit_stats_sizeof_args() != ctypes.sizeof(FitStatsArgs)):
         raise RuntimeError("FitStatsArgs layout mismatch between HIP library and Python")
+    if (getattr(lib, "dml_rank_stats_sizeof_args", None) is not None
+            and lib.dml_rank_stats_sizeof_args() != ctypes.sizeof(RankStatsArgs)):
+        raise RuntimeError("RankStatsArgs layout mismatch between HIP library and Python")
     if getattr(lib, "dml_mae_sizeof_args", None) is not None and lib.dml_mae_sizeof_args() != ctypes.sizeof(MaeArgs):
         raise RuntimeError("MAE builder argument layout mismatch between HIP library and Python")
     if getattr(lib, "dml_lr_sizeof_fwd_args", None) is not None:
