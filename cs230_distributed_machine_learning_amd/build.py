@@ -212,6 +212,28 @@ def build_rank_selftest(force: bool = False) -> str:
     return RANK_SAN_EXE
 
 
+ENET_SAN_EXE = os.path.join(LIB, "enet_selftest_asan")
+
+
+def build_enet_selftest(force: bool = False) -> str:
+    """``csrc/runtime/enet_cpu.cpp`` + ``csrc/tests/enet_selftest.cpp`` with AddressSanitizer and
+    UndefinedBehaviorSanitizer, as ``build_rank_selftest``: a stand-alone executable; any report
+    aborts it."""
+    srcs = [os.path.join(CSRC, "runtime", "enet_cpu.cpp"), os.path.join(CSRC, "tests", "enet_selftest.cpp")]
+    deps = srcs + [os.path.join(CSRC, "kernels", "enet_args.h")]
+    os.makedirs(LIB, exist_ok=True)
+    cxx = os.environ.get("CXX", shutil.which("g++") or "c++")
+    flags = [cxx, "-O1", "-g", "-std=c++17", "-fopenmp", "-ffp-contract=off", "-fsanitize=address,undefined",
+             "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
+    with _BuildLock():
+        if force or _stale_by_hash(ENET_SAN_EXE, deps, flags):
+            tmp = _tmp(ENET_SAN_EXE)
+            _run([*flags, "-I", os.path.join(CSRC, "kernels"), *srcs, "-o", tmp])
+            os.replace(tmp, ENET_SAN_EXE)
+            _stamp(ENET_SAN_EXE, deps, flags)
+    return ENET_SAN_EXE
+
+
 def build_all(force: bool = False) -> tuple[str, str]:
     return build_cpu(force), build_hip(force)
 
@@ -230,6 +252,7 @@ if __name__ == "__main__":
     if args.sanitize:
         print(build_sanitized(args.force))
         print(build_rank_selftest(args.force))
+        print(build_enet_selftest(args.force))
     print(build_cpu(args.force))
     if not args.cpu_only:
         print(build_hip(args.force))

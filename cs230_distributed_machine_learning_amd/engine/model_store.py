@@ -327,6 +327,36 @@ class Predictor:
             raise AttributeError(f"{self.model_type} artefact has no {name} (fit with oob_score=True, bootstrap=True)")
         return v
 
+    # ---- fitted linear-regression attributes (LinearRegression, Ridge, Lasso, ElasticNet) -----
+    def _linreg(self, name: str):
+        if self.kind != "linear_regression":
+            raise AttributeError(f"{self.model_type} artefact has no {name}")
+        return self.model
+
+    @property
+    def coef_(self) -> np.ndarray:
+        return np.asarray(self._linreg("coef_")["coef"], dtype=np.float64)
+
+    @property
+    def intercept_(self) -> float:
+        return float(self._linreg("intercept_")["intercept"])
+
+    @property
+    def n_iter_(self) -> int:
+        """Lasso / ElasticNet: coordinate-descent sweeps run (docs/ELASTIC_NET.md)."""
+        v = self._linreg("n_iter_").get("n_iter")
+        if v is None:
+            raise AttributeError(f"{self.model_type} artefact has no n_iter_")
+        return int(v)
+
+    @property
+    def dual_gap_(self) -> float:
+        """Lasso / ElasticNet: the last duality gap divided by the training rows (sklearn's)."""
+        v = self._linreg("dual_gap_").get("dual_gap")
+        if v is None:
+            raise AttributeError(f"{self.model_type} artefact has no dual_gap_")
+        return float(v)
+
     @property
     def oob_score_(self) -> float:
         """Forests: the out-of-bag score.  GradientBoosting: the last ``oob_scores_`` (a loss)."""

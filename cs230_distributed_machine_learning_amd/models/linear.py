@@ -1,4 +1,5 @@
-"""LogisticRegression and LinearRegression families — every fit of a job solved at once.
+"""LogisticRegression, LinearRegression and Ridge / Lasso / ElasticNet families — every fit of a
+job solved at once.
 
 Reference: both are whitelisted estimators fitted one (candidate, fold) at a time by
 sklearn on CPU (aws-prod/worker/worker.py:39,46 whitelist; :315, :326/:341 fits).
@@ -19,6 +20,10 @@ LinearRegression
     pseudo-inverse (min-norm like sklearn's lstsq).  On the GPU every split's moments
     come from one fused pass over X (``dml_split_moments``: f64 MFMA tiles, split
     masks from the role rows, shifted by the column means for an accurate centring).
+Ridge / Lasso / ElasticNet
+    Functions of the same moments (``PenalizedLinearFamily``, docs/ELASTIC_NET.md): Ridge from
+    one ``eigh`` per split, Lasso / ElasticNet by sklearn's Gram coordinate descent for every
+    (candidate, split) in one launch (``dml_enet_cd``, csrc/kernels/enet.hip).
 """
 from __future__ import annotations
 
@@ -1339,5 +1344,277 @@ class LinearRegressionFamily(Family):
         return w, ym - xm @ w
 
 
+_ENET_DEFAULTS = {"alpha": 1.0, "l1_ratio": 0.5, "fit_intercept": True, "precompute": False, "max_iter": 1000,
+                  "copy_X": True, "tol": 1e-4, "warm_start": False, "positive": False, "random_state": None,
+                  "selection": "cyclic"}
+_RIDGE_DEFAULTS = {"alpha": 1.0, "fit_intercept": True, "copy_X": True, "max_iter": None, "tol": 1e-4,
+                   "solver": "auto", "positive": False, "random_state": None}
+_RIDGE_SOLVERS = ("auto", "svd", "cholesky", "lsqr", "sparse_cg", "sag", "saga", "lbfgs")
+SELECTION_RANDOM = "selection='random' runs cyclic coordinate descent (same optimum to tol)"
+NO_L1 = ("Coordinate descent without L1 regularization may lead to unexpected results and is discouraged. "
+         "Set l1_ratio > 0 to add L1 regularization.")
+
+
+def _sk_range(v, name, model_type, lo, hi=None):
+    """A float parameter checked as sklearn's parameter validation words it."""
+    rng = f"[{lo}, inf)" if hi is None else f"[{lo}, {hi}]"
+    msg = f"The {name!r} parameter of {model_type} must be a float in the range {rng}. Got {v!r} instead."
+    try:
+        return as_float(v, name, lo=lo, hi=hi)
+    except ParamError:
+        raise ParamError(msg) from None
+
+
+def host_split_moments(data, splits: List[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``LinearRegressionFamily.split_moments`` in plain float64 torch (the CPU data path):
+    every split's train-row moments of z = [x - c, 1, y - c_y], c = the column means."""
+    X, y = data.X.double(), data.y_reg.double()
+    shift = torch.cat([X.mean(0), y.mean().view(1)])
+    d = data.d
+    Z = torch.cat([X - shift[:d], torch.ones((X.shape[0], 1), dtype=torch.float64, device=X.device),
+                   (y - shift[d]).view(-1, 1)], 1)
+    M = torch.stack([Z[data.train_rows[s].long()].t() @ Z[data.train_rows[s].long()] for s in splits]) \
+        if splits else torch.zeros((0, d + 2, d + 2), dtype=torch.float64, device=X.device)
+    return M, shift
+
+
+class PenalizedLinearFamily(Family):
+    """Ridge, Lasso and ElasticNet from the split moments (docs/ELASTIC_NET.md).
+
+    One moments pass per batch (``dml_split_moments`` on the GPU, streamed for binned-only
+    tables, float64 torch on the CPU) gives every split's count, sums, X^T X, X^T y and y^T y;
+    all three estimators are functions of those.  Ridge: one ``eigh`` per (split,
+    fit_intercept), every alpha from it.  Lasso / ElasticNet: sklearn's Gram coordinate descent
+    for every (candidate, split) at once -- ``dml_enet_cd`` on the device, its bit-equal host
+    twin on the CPU -- with the moments never read back."""
+
+    model_types = ("Ridge", "Lasso", "ElasticNet")
+    classifiers = ()
+    data_parallel = False   # row-sharded moments are not implemented: such a job runs task-parallel
+    streams_rows = True     # binned-only tables: moments and predictions over streamed host rows
+
+    def resolve(self, model_type, params, n_train, n_features, n_classes):
+        defaults = _RIDGE_DEFAULTS if model_type == "Ridge" else {
+            k: v for k, v in _ENET_DEFAULTS.items() if model_type != "Lasso" or k != "l1_ratio"}
+        p = dict(defaults)
+        p.update({k: v for k, v in params.items() if k in defaults})
+        warn = []
+        unknown = sorted(k for k in params if k not in defaults)
+        if unknown:
+            warn.append(f"ignored unknown parameters {unknown}")
+        alpha = _sk_range(p["alpha"], "alpha", model_type, 0.0)
+        fi = as_bool(p["fit_intercept"], "fit_intercept")
+        if model_type == "Ridge":
+            if p["solver"] not in _RIDGE_SOLVERS:
+                raise ParamError(f"The 'solver' parameter of Ridge must be a str among {set(_RIDGE_SOLVERS)}. "
+                                 f"Got {p['solver']!r} instead.")
+            if as_bool(p["positive"], "positive"):
+                raise ParamError("positive=True is not supported for Ridge (sklearn solves it with lbfgs only)")
+            return {"alpha": alpha, "fit_intercept": fi, "warnings": warn}
+        l1_ratio = 1.0 if model_type == "Lasso" else _sk_range(p["l1_ratio"], "l1_ratio", model_type, 0.0, 1.0)
+        if p["selection"] not in ("cyclic", "random"):
+            raise ParamError(f"The 'selection' parameter of {model_type} must be a str among "
+                             f"{{'cyclic', 'random'}}. Got {p['selection']!r} instead.")
+        if p["selection"] == "random":
+            warn.append(SELECTION_RANDOM)
+        if alpha * l1_ratio == 0.0:
+            warn.append(NO_L1)
+        return {"alpha": alpha, "l1_ratio": l1_ratio, "fit_intercept": fi,
+                "positive": as_bool(p["positive"], "positive"),
+                "max_iter": as_int(p["max_iter"], "max_iter", lo=1), "tol": _sk_range(p["tol"], "tol", model_type, 0.0),
+                "warnings": warn}
+
+    def cost(self, model_type, rp, n_train, n_features, n_classes) -> float:
+        # the moments pass (LinearRegression's price) is shared by every candidate of the job, and
+        # cost() is not told how many there are: a candidate carries a fixed eighth of it (an
+        # arbitrary share, as KNN's fixed share of its one search is), plus its own sweeps
+        d2 = n_features * n_features
+        return n_train * d2 * 2e-12 / 8 + d2 * min(rp.get("max_iter", 1), 100) * 1e-11 + 1e-3
+
+    # --------------------------------------------------------------------------------
+    @staticmethod
+    def _moments(data, splits):
+        if data.X is None:
+            if not getattr(data, "can_stream_rows", lambda: False)():
+                raise ParamError("Ridge / Lasso / ElasticNet need the float32 rows (this table arrived as bins only)")
+            return streamed_split_moments(data, splits)
+        if data.is_gpu:
+            return LinearRegressionFamily.split_moments(data, splits)
+        return host_split_moments(data, splits)
+
+    @staticmethod
+    def _grams(M, shift, d, keys, splits):
+        """Per (split, fit_intercept) of ``keys``: the Gram A [K, d, d], b [K, d], y^T y [K] the
+        solvers work on and (xm, ym) [K, d], [K] the intercept needs -- device tensors, no host
+        read.  Coordinates whose Gram diagonal is round-off (a column constant on the split's
+        training rows) have their row, column and b entry set to exactly 0; the last result is
+        that mask (1 = kept) [K, d]."""
+        cx, cy = shift[:d], shift[d]
+        A_l, b_l, yy_l, xm_l, ym_l, live_l = [], [], [], [], [], []
+        eps = torch.finfo(torch.float64).eps
+        for sp, fi in keys:
+            m = M[splits.index(sp)]
+            cnt, Sx, Sy = m[d, d], m[:d, d], m[d + 1, d]
+            XX, Xy, YY = m[:d, :d], m[:d, d + 1], m[d + 1, d + 1]
+            if fi:
+                xm, ym = Sx / cnt.clamp_min(1), Sy / cnt.clamp_min(1)
+                A = XX - cnt * torch.outer(xm, xm)
+                b = Xy - cnt * xm * ym
+                yy = YY - cnt * ym * ym
+                scale = XX.diagonal()
+                xm_l.append(xm + cx)
+                ym_l.append(ym + cy)
+            else:   # moments about the origin: x = z + c_x, y = z_y + c_y
+                A = XX + torch.outer(Sx, cx) + torch.outer(cx, Sx) + cnt * torch.outer(cx, cx)
+                b = Xy + Sx * cy + cx * Sy + cnt * cx * cy
+                yy = YY + 2.0 * cy * Sy + cnt * cy * cy
+                scale = A.diagonal()
+                xm_l.append(torch.zeros_like(cx))
+                ym_l.append(torch.zeros_like(cy))
+            live = (A.diagonal() > 64.0 * eps * scale).to(A.dtype)
+            A_l.append(A * live.view(-1, 1) * live.view(1, -1))
+            b_l.append(b * live)
+            yy_l.append(yy.clamp_min(0.0))
+            live_l.append(live)
+        return (torch.stack(A_l).contiguous(), torch.stack(b_l).contiguous(), torch.stack(yy_l), torch.stack(xm_l),
+                torch.stack(ym_l), torch.stack(live_l))
+
+    @staticmethod
+    def _ridge(A, b, alphas: List[float]) -> torch.Tensor:
+        """[len(alphas), d]: w(alpha) = V diag(1 / (lambda + alpha)) V^T b from ONE eigh of A;
+        alpha = 0 is the minimum-norm least squares of ``_ls_solve``."""
+        out = torch.empty((len(alphas), A.shape[0]), dtype=torch.float64, device=A.device)
+        pos = [i for i, a in enumerate(alphas) if a > 0]
+        if pos:
+            lam, V = torch.linalg.eigh(A)
+            al = torch.tensor([alphas[i] for i in pos], dtype=torch.float64, device=A.device)
+            coef = (V.t() @ b).view(-1, 1) / (lam.clamp_min(0.0).view(-1, 1) + al.view(1, -1))
+            out[torch.tensor(pos, device=A.device)] = (V @ coef).t()
+        for i, a in enumerate(alphas):
+            if a == 0:
+                out[i] = _ls_solve(A, b, False)
+        return out
+
+    @staticmethod
+    def _enet(A, b, yy, gid, l1, l2, positive, max_iter, tol):
+        """Every Lasso / ElasticNet problem of the batch: the kernel on a GPU, the host twin on
+        the CPU -- and for a d above the kernel's limit, after one read-back of the Grams.
+        Returns ((w, gap, tol_eff, n_iter) on A's device, "kernel" or "twin")."""
+        from ..ops import enet_ops
+
+        args = (torch.tensor(gid, dtype=torch.int32), torch.tensor(l1, dtype=torch.float64),
+                torch.tensor(l2, dtype=torch.float64), torch.tensor(positive, dtype=torch.int32),
+                torch.tensor(max_iter, dtype=torch.int32), torch.tensor(tol, dtype=torch.float64))
+        if A.is_cuda:
+            try:   # the per-problem arguments go up from pinned memory: the launch needs no host sync
+                return enet_ops.enet_cd(A, b, yy, *[t.pin_memory().to(A.device, non_blocking=True) for t in args]), \
+                    "kernel"
+            except enet_ops.EnetTooLarge:
+                dev = A.device
+                return tuple(t.to(dev) for t in enet_ops.enet_cd(A.cpu(), b.cpu(), yy.cpu(), *args)), "twin"
+        return enet_ops.enet_cd(A, b, yy, *args), "twin"
+
+    def run(self, data, tasks: List[FitTask], keep_models: bool = False) -> List[FitOutput]:
+        if not tasks:
+            return []
+        if data.classification:
+            raise ParamError(f"{tasks[0].model_type} needs a regression target")
+        t0 = time.perf_counter()
+        d, dev = data.d, data.device
+        splits = sorted({t.split for t in tasks})
+        with trace.range("enet_moments"):
+            M, shift = self._moments(data, splits)
+        keys = sorted({(t.split, bool(t.params["fit_intercept"])) for t in tasks})
+        A, b, yy, xm, ym, live = self._grams(M, shift, d, keys, splits)
+        W = torch.zeros((len(tasks), d), dtype=torch.float64, device=dev)
+        gid_of = [keys.index((t.split, bool(t.params["fit_intercept"]))) for t in tasks]
+        # Ridge: every alpha of a Gram from one eigendecomposition
+        by_gram: Dict[int, List[int]] = {}
+        for i, t in enumerate(tasks):
+            if t.model_type == "Ridge":
+                by_gram.setdefault(gid_of[i], []).append(i)
+        with trace.range("ridge_solve"):
+            for g, idx in by_gram.items():
+                # an eigenvector of a zeroed coordinate is e_j only to round-off: its coefficient is exactly 0
+                W[torch.tensor(idx, device=dev)] = self._ridge(A[g], b[g], [tasks[i].params["alpha"] for i in idx]) * live[g]
+        # Lasso / ElasticNet: one launch for every problem of the batch
+        cd = [i for i, t in enumerate(tasks) if t.model_type != "Ridge"]
+        n_iter_h, gap_h, tol_h = {}, {}, {}
+        if cd:
+            n_tr = [float(data.train_counts[tasks[i].split]) for i in cd]
+            rp = [tasks[i].params for i in cd]
+            with trace.range("enet_solve"):
+                (w, gap, tol_eff, n_iter), solver = self._enet(
+                    A, b, yy, [gid_of[i] for i in cd],
+                    [p["alpha"] * p["l1_ratio"] * n for p, n in zip(rp, n_tr)],
+                    [p["alpha"] * (1.0 - p["l1_ratio"]) * n for p, n in zip(rp, n_tr)],
+                    [int(p["positive"]) for p in rp], [p["max_iter"] for p in rp], [p["tol"] for p in rp])
+            W[torch.tensor(cd, device=dev)] = w
+            gh, th, nh = gap.cpu().tolist(), tol_eff.cpu().tolist(), n_iter.cpu().tolist()   # results only
+            for k, i in enumerate(cd):
+                n_iter_h[i], gap_h[i], tol_h[i] = int(nh[k]), float(gh[k]), float(th[k])
+        gsel = torch.tensor(gid_of, device=dev)
+        b0 = ym[gsel] - (xm[gsel] * W).sum(1)    # 0 without an intercept (xm = ym = 0 there)
+        with trace.range("enet_predict"):
+            preds = self._predict(data, tasks, W, b0)
+        outs = []
+        W_h, b0_h = (W.cpu().numpy(), b0.cpu().numpy()) if keep_models else (None, None)
+        for i, t in enumerate(tasks):
+            warn = list(t.params.get("warnings", []))
+            info: Dict[str, Any] = {"warnings": warn}
+            if i in n_iter_h:
+                info["n_iter"] = n_iter_h[i]
+                info["solver"] = solver   # "kernel" (dml_enet_cd) or "twin" (dml_cpu_enet_cd)
+                if not gap_h[i] < tol_h[i]:
+                    warn.append(f"Objective did not converge (duality gap {gap_h[i]:.3e}, tolerance {tol_h[i]:.3e}); "
+                                f"increase max_iter")
+            o = FitOutput(task_id=t.task_id, pred=preds[i], info=info)
+            if keep_models:
+                o.model = {"kind": "linear_regression", "coef": W_h[i].copy(), "intercept": float(b0_h[i]),
+                           "model_type": t.model_type,
+                           "params": {k: v for k, v in t.params.items() if k != "warnings"}}
+                if i in n_iter_h:
+                    o.model["n_iter"] = n_iter_h[i]
+                    o.model["dual_gap"] = gap_h[i] / max(1.0, float(data.train_counts[t.split]))
+            outs.append(o)
+        if data.is_gpu:
+            torch.cuda.synchronize(dev)
+        dt = time.perf_counter() - t0
+        for o in outs:
+            o.fit_seconds = dt / len(outs)
+        return outs
+
+    @staticmethod
+    def _predict(data, tasks, W, b0) -> List[torch.Tensor]:
+        """Held-out predictions of every task: per split ONE float64 product of the split's test
+        rows (in row chunks) with the matrix of all that split's coefficient vectors."""
+        dev = data.device
+        by_split: Dict[int, List[int]] = {}
+        for i, t in enumerate(tasks):
+            by_split.setdefault(t.split, []).append(i)
+        preds: List[torch.Tensor] = [None] * len(tasks)
+        empty = lambda k: torch.zeros((0, k), dtype=torch.float32, device=dev)
+        if data.X is None:   # binned-only: one pass over the host rows for every split
+            order = sorted(by_split)
+            cols = {s: torch.tensor(by_split[s], device=dev) for s in order}
+            res = streamed_test_many(data, [(s, lambda Xt, c=cols[s]: (Xt @ W[c].t() + b0[c]).float()) for s in order])
+            blocks = {s: (r if r is not None else empty(len(by_split[s]))) for s, r in zip(order, res)}
+        else:
+            blocks = {}
+            for s, idx in by_split.items():
+                c = torch.tensor(idx, device=dev)
+                Wc, bc = W[c].t().contiguous(), b0[c]
+                te = data.test_rows[s].long()
+                step = max(1024, (1 << 29) // (8 * (data.d + 2 + len(idx))))   # float64 copies <= ~512 MB
+                parts = [(data.X[te[r:r + step]].double() @ Wc + bc).float() for r in range(0, len(te), step)]
+                blocks[s] = torch.cat(parts) if parts else empty(len(idx))
+        for s, idx in by_split.items():
+            Pt = blocks[s].t().contiguous()
+            for k, i in enumerate(idx):
+                preds[i] = Pt[k]
+        return preds
+
+
 register(LogisticFamily())
 register(LinearRegressionFamily())
+register(PenalizedLinearFamily())

@@ -152,6 +152,13 @@ MaeArgs = _i64_struct(
      "rows_b", "nodes", "vals", "nabs", "pool_cap", "open_a", "open_b", "open_cap", "counters", "tree_W",
      "n_nodes_out", "levels_out", "status_out", "big_a", "big_b", "big_cap", "res", "P", "big_rows"],
 )
+# csrc/kernels/enet_args.h EnetArgs (batched Gram coordinate descent: enet.hip and its host twin)
+EnetArgs = _i64_struct(
+    "EnetArgs",
+    ["Q", "q", "ynorm2", "gram_id", "l1", "l2", "positive", "max_iter", "tol", "w", "gap", "tol_eff", "n_iter",
+     "F", "d", "G"],
+)
+ENET_D_TOO_LARGE = 3   # dml_enet_cd: d above dml_enet_max_d(), nothing was launched
 LrGradArgs = _i64_struct("LrGradArgs", ["rh", "rl", "unused", "xth", "xtl", "m_tiles", "n_tiles", "Kp", "S", "Kc", "out",
                                         "bk_off", "slab0", "mlive", "kskip"])
 
@@ -216,6 +223,11 @@ def cpu_lib() -> ctypes.CDLL:
             lib.dml_cpu_dp_sizeof_args.restype = c_i32
             lib.dml_cpu_dp_step.restype = c_i32
             lib.dml_cpu_dp_step.argtypes = [c_vp, c_i32]
+            lib.dml_cpu_enet_sizeof_args.restype = c_i32
+            if lib.dml_cpu_enet_sizeof_args() != ctypes.sizeof(EnetArgs):
+                raise RuntimeError("EnetArgs layout mismatch between C++ and Python")
+            lib.dml_cpu_enet_cd.restype = c_i32
+            lib.dml_cpu_enet_cd.argtypes = [ctypes.POINTER(EnetArgs)]
             _cpu = lib
         return _cpu
 
@@ -343,6 +355,11 @@ def _register_optional(lib) -> None:
         "dml_mae_sizeof_res": (c_i32, []),
         "dml_mae_count": (c_i32, [ctypes.POINTER(MaeArgs), c_vp]),
         "dml_mae_build": (c_i32, [ctypes.POINTER(MaeArgs), c_vp]),
+        "dml_enet_sizeof_args": (c_i32, []),
+        "dml_enet_max_d": (c_i32, []),
+        "dml_enet_problems_per_block": (c_i32, [c_i64]),
+        "dml_enet_cd": (c_i32, [ctypes.POINTER(EnetArgs), c_vp]),
+        "dml_enet_cd_plain": (c_i32, [ctypes.POINTER(EnetArgs), c_vp]),
     }
     for name, (res, args) in table.items():
         fn = getattr(lib, name, None)
@@ -362,6 +379,9 @@ def _register_optional(lib) -> None:
     if (getattr(lib, "dml_rank_stats_sizeof_args", None) is not None
             and lib.dml_rank_stats_sizeof_args() != ctypes.sizeof(RankStatsArgs)):
         raise RuntimeError("RankStatsArgs layout mismatch between HIP library and Python")
+    if (getattr(lib, "dml_enet_sizeof_args", None) is not None
+            and lib.dml_enet_sizeof_args() != ctypes.sizeof(EnetArgs)):
+        raise RuntimeError("EnetArgs layout mismatch between HIP library and Python")
     if getattr(lib, "dml_mae_sizeof_args", None) is not None and lib.dml_mae_sizeof_args() != ctypes.sizeof(MaeArgs):
         raise RuntimeError("MAE builder argument layout mismatch between HIP library and Python")
     if getattr(lib, "dml_lr_sizeof_fwd_args", None) is not None:
