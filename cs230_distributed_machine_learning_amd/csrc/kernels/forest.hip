@@ -142,8 +142,19 @@ template <int MODE> constexpr int block_nt() { return MODE == 1 ? DML_BLOCK_NT :
 #ifndef DML_GINI_PF
 #define DML_GINI_PF 1          // binary Gini: fp32 pre-filter of candidate bins (eval_feature)
 #endif
+#ifndef DML_EVAL_SEG
+// fused node kernels, binary Gini pre-filter evaluation: 2 scores two features per wave pass
+// (eval_gini_seg: 32-lane segments of 8 bins per lane), 4 scores fours, then a pair (16-lane
+// segments of 16 bins per lane); a feature left over goes through eval_gini_pf.  0: one feature
+// per pass (A/B builds; docs/EVAL_SEG.md)
+#define DML_EVAL_SEG 2
+#endif
+#ifdef DML_X2_EVAL             // the sensitivity build doubles the one-feature loop
+#undef DML_EVAL_SEG
+#define DML_EVAL_SEG 0
+#endif
 #ifndef DML_WAVE_PREFETCH
-#define DML_WAVE_PREFETCH 12   // wave tier: visiting positions whose bins are gathered up front
+#define DML_WAVE_PREFETCH 12  // wave tier: visiting positions whose bins are gathered up front
 #endif
 
 // optional per-phase cycle accounting of the fused node kernel (-DDML_PHASE_PROF builds only)
@@ -714,6 +725,159 @@ __device__ DML_EVAL_ATTR void eval_gini_pf(CT* h, int span, const NodeSpec& s, i
   }
 }
 
+// argmax over (gain desc, idx asc) inside aligned segments of SL lanes: every lane ends with
+// its segment's pair (wave::argmax without the steps that cross a segment)
+template <int SL>
+__device__ __forceinline__ void seg_argmax(double& g, int& idx, int lane) {
+#define DML_SEG_ARGMAX_STEP(M)                                       \
+  if constexpr (SL > M) {                                            \
+    const double og = wave::shfl_xor<M>(g, lane);                    \
+    const int oi = wave::shfl_xor<M>(idx, lane);                     \
+    if (og > g || (og == g && (unsigned)oi < (unsigned)idx)) {       \
+      g = og;                                                        \
+      idx = oi;                                                      \
+    }                                                                \
+  }
+  DML_SEG_ARGMAX_STEP(16) DML_SEG_ARGMAX_STEP(8) DML_SEG_ARGMAX_STEP(4) DML_SEG_ARGMAX_STEP(2) DML_SEG_ARGMAX_STEP(1)
+#undef DML_SEG_ARGMAX_STEP
+}
+
+// eval_gini_pf for NSEG = 2 or 4 features in ONE wave pass.  The wave is cut into NSEG segments
+// of SL = 64 / NSEG lanes; segment q owns the histogram h + 256 q and writes outputs q (rleft
+// CH apart); a lane holds B = 4 NSEG consecutive bins, so it reads words [B lane, B lane + B)
+// of the NSEG contiguous histograms.  What one feature costs beyond its bins' scores -- the DPP
+// scan, the fp32 max reduction, the re-score loop, the argmax and the output stores -- is paid
+// once per pass.  Every value is the one eval_gini_pf computes: the same integer prefix sums
+// (the scan stops at the segment: row_shr 1/2/4/8, plus row_bcast:15 into the odd rows of
+// 32-lane segments), the same fp32 score, segment maximum and 2^-14 threshold, the same fp64
+// re-score in ascending bins with strict >, and (gain desc, bin asc) among a segment's lanes.
+// The lane that owns the winning bin keeps its cumulative word and writes the segment's
+// outputs itself (the segment's first lane if no bin is admissible).
+template <int NSEG, class CT>
+__device__ DML_EVAL_ATTR void eval_gini_seg(CT* h, const NodeSpec& s, int lane, double* out_gain, int* out_bin,
+                                            int* out_nc, double* out_left, int CH, bool zero_after, double cw0,
+                                            double cw1) {
+  static_assert(NSEG == 2 || NSEG == 4, "two 32-lane or four 16-lane segments");
+  constexpr int B = 4 * NSEG, SL = 64 / NSEG;
+  const int l = lane & (SL - 1), q = lane / SL;
+  CT v[B];
+#pragma unroll
+  for (int i = 0; i < B; ++i) v[i] = h[B * lane + i];
+  if (zero_after) {
+#pragma unroll
+    for (int i = 0; i < B; ++i) h[B * lane + i] = (CT)0;
+  }
+  uint32_t nz = 0;
+#pragma unroll
+  for (int i = 0; i < B; ++i) nz |= v[i] != (CT)0 ? (1u << i) : 0u;
+#pragma unroll
+  for (int i = 1; i < B; ++i) v[i] += v[i - 1];
+  CT t = v[B - 1];
+  if constexpr (sizeof(CT) == 8) {
+    uint64_t x = (uint64_t)t;
+    x = wave::scan_step_u64<wave::kRowShr + 1, 0xF>(x);
+    x = wave::scan_step_u64<wave::kRowShr + 2, 0xF>(x);
+    x = wave::scan_step_u64<wave::kRowShr + 4, 0xF>(x);
+    x = wave::scan_step_u64<wave::kRowShr + 8, 0xF>(x);
+    if constexpr (SL == 32) x = wave::scan_step_u64<wave::kRowBcast15, 0xA>(x);
+    t = (CT)x;
+  } else {
+    t += wave::dpp<wave::kRowShr + 1>(t);
+    t += wave::dpp<wave::kRowShr + 2>(t);
+    t += wave::dpp<wave::kRowShr + 4>(t);
+    t += wave::dpp<wave::kRowShr + 8>(t);
+    if constexpr (SL == 32) t += wave::dpp<wave::kRowBcast15, 0xA>(t);
+  }
+  {
+    const CT sh = wave::excl_from_incl<CT>(t);
+    const CT ex = l == 0 ? (CT)0 : sh;
+#pragma unroll
+    for (int i = 0; i < B; ++i) v[i] += ex;
+  }
+  // the segment's total, from its last lane
+  CT tv = wave::bcast<CT>(t, SL - 1);
+#pragma unroll
+  for (int k = 1; k < NSEG; ++k) {
+    const CT tk = wave::bcast<CT>(t, (k + 1) * SL - 1);
+    tv = q == k ? tk : tv;
+  }
+  const uint32_t mslu = (uint32_t)s.min_samples_leaf;
+  const float cw0f = (float)cw0, cw1f = (float)cw1;
+  const bool mwl = s.min_weight_leaf > 0.0;
+  const uint32_t tr = pk_rows<CT>(tv), t0i = pk_w0<CT>(tv), t1i = pk_w1<CT>(tv);
+  const double t0 = (double)t0i * cw0, t1 = (double)t1i * cw1;
+  float sq[B], qm = -INFINITY;
+  bool nc = false;
+#pragma unroll
+  for (int i = 0; i < B; ++i) {
+    const CT cv = v[i];
+    const uint32_t rl = pk_rows<CT>(cv), rr = tr - rl;
+    const uint32_t l0i = pk_w0<CT>(cv), l1i = pk_w1<CT>(cv);
+    nc |= (rl > 0u && rr > 0u);
+    bool ok = ((nz >> i) & 1u) && (l * B + i) != 255 && rl >= mslu && rr >= mslu;
+    if (mwl) {
+      const double l0 = (double)l0i * cw0, l1 = (double)l1i * cw1;
+      ok = ok && !side_too_light(s, l0 + l1, (t0 - l0) + (t1 - l1));
+    }
+    const float a0 = (float)l0i * cw0f, a1 = (float)l1i * cw1f;
+    const float r0 = (float)(t0i - l0i) * cw0f, r1 = (float)(t1i - l1i) * cw1f;
+    const float wl = a0 + a1, wr = r0 + r1;
+    const float num = (a0 * a0 + a1 * a1) * wr + (r0 * r0 + r1 * r1) * wl;
+    sq[i] = ok ? num * __builtin_amdgcn_rcpf(wl * wr) : -INFINITY;
+    qm = fmaxf(qm, sq[i]);
+  }
+  if constexpr (SL == 32) qm = fmaxf(qm, wave::shfl_xor<16>(qm, lane));
+  qm = fmaxf(qm, wave::shfl_xor<8>(qm, lane)); qm = fmaxf(qm, wave::shfl_xor<4>(qm, lane));
+  qm = fmaxf(qm, wave::shfl_xor<2>(qm, lane)); qm = fmaxf(qm, wave::shfl_xor<1>(qm, lane));
+  const float thr = qm - qm * 0x1p-14f;
+  uint32_t m = 0;
+#pragma unroll
+  for (int i = 0; i < B; ++i) m |= (sq[i] >= thr && sq[i] != -INFINITY) ? (1u << i) : 0u;
+  double best = -INFINITY;
+  int bb = -1;
+  CT bcv = (CT)0;
+  while (__ballot(m != 0u) != 0ull) {
+    if (m != 0u) {
+      const int i = __builtin_ctz(m);
+      m &= m - 1u;
+      CT cv = v[0];
+#pragma unroll
+      for (int k = 1; k < B; ++k) cv = i == k ? v[k] : cv;
+      const double l0 = (double)pk_w0<CT>(cv) * cw0, l1 = (double)pk_w1<CT>(cv) * cw1;
+      ClsAcc L, R;
+      L.init(kGini); R.init(kGini);
+      L.add(l0); L.add(l1);
+      R.add(t0 - l0); R.add(t1 - l1);
+      const double g = cls_proxy(L, R, kGini);
+      if (g > best) { best = g; bb = l * B + i; bcv = cv; }
+    }
+  }
+  constexpr uint64_t kSegMask = SL == 32 ? 0xFFFFFFFFull : 0xFFFFull;
+  const uint64_t cm = __ballot(bb >= 0);
+  bool one_each = true;   // no segment has two lanes with a contender (the usual case)
+#pragma unroll
+  for (int k = 0; k < NSEG; ++k) one_each = one_each && __popcll((cm >> (k * SL)) & kSegMask) <= 1;
+  bool writer;
+  if (one_each) {
+    // the lane that holds its segment's only contender is the winner as it stands
+    const bool has = (uint32_t)((cm >> (q * SL)) & kSegMask) != 0u;
+    writer = has ? bb >= 0 : l == 0;
+  } else {
+    const int mine = bb;
+    seg_argmax<SL>(best, bb, lane);
+    writer = bb >= 0 ? mine == bb : l == 0;
+  }
+  const uint64_t ncm = __ballot(nc);
+  const bool any_nc = (uint32_t)((ncm >> (q * SL)) & kSegMask) != 0u;
+  if (writer) {
+    double* ol = out_left + q * CH;
+    ol[0] = bb >= 0 ? (double)pk_w0<CT>(bcv) * cw0 : 0.0;
+    ol[1] = bb >= 0 ? (double)pk_w1<CT>(bcv) * cw1 : 0.0;
+    ol[2] = bb >= 0 ? (double)pk_rows<CT>(bcv) : 0.0;
+    out_gain[q] = best; out_bin[q] = bb; out_nc[q] = any_nc ? 1 : 0;
+  }
+}
+
 // ONE wave evaluates one feature's histogram.  Binary (MODE 1) and regression (MODE 2)
 // histograms are read ONCE into registers (4 bins per lane), scanned with DPP, scored and
 // arg-maxed without writing the scan back to LDS; the histogram is cleared by the same
@@ -1249,6 +1413,17 @@ __device__ __forceinline__ uint32_t* plane_word(uint8_t* plane, int p) {
   return (uint32_t*)(plane + 4u * (uint32_t)p);
 }
 
+// Features per evaluation pass of one binary k_nodes instantiation under DML_EVAL_SEG, bounded
+// by its registers (profiles/r13_eval_seg_registers.txt).  The wave tier's generic-criterion
+// kernels sit at the 128-VGPR cap with 52 / 72 B of scratch and two features per pass raise
+// that to 80 / 76 B: they keep the one-feature loop.  Four per pass (16 bins per lane) spill
+// 76 .. 244 B everywhere but in the Gini-specialised narrow-word wave kernel (60 B).
+template <int NT, int FC, bool H32>
+constexpr int eval_seg_of() {
+  if (DML_EVAL_SEG == 0 || (NT == 64 && FC < 0)) return 0;
+  return (DML_EVAL_SEG == 4 && NT == 64 && H32) ? 4 : 2;
+}
+
 // H32 (wave tier of a binary build whose wave_max <= kPack32MaxRows): the narrow u32 word
 template <int NT, int MODE, int FC, bool H32 = false>
 __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? DML_NODES_WPE_REG : (MODE == 0 ? DML_NODES_WPE_MC : (NT == 64 ? DML_NODES_WPE_WAVE : DML_NODES_WPE)), (MODE == 1 && NT == 64) ? DML_NODES_WPE_WAVE_MAX : 8))) void k_nodes(Ctx c, int tier, int set_cur,
@@ -1257,6 +1432,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
   using CT = typename std::conditional<H32, uint32_t, typename HT<MODE>::T>::type;
   constexpr bool PK = FC >= 0;   // specialised builds have packed row words
   constexpr int NW = NT / 64;
+  constexpr int ESEG = eval_seg_of<NT, FC, H32>();
   constexpr int RPT = NT == 64 ? 4 : 1;   // wave tier: rows per thread in registers (packed u8 x 4)
   static_assert(2 * RPT * (NT / 64) <= 32, "Scratch::wcnt too small for this NT x RPT");
   constexpr int KGMAX = NT == 64 ? (H32 ? DML_KGMAX_WAVE32 : DML_KGMAX_WAVE) : DML_KGMAX_BLOCK;   // feature-group bound (register-resident bins)
@@ -1644,8 +1820,34 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
     }
     __syncthreads();
     PH(2)
-    for (int j = wid; j < g; j += NW) {
-#ifdef DML_X2_EVAL   // sensitivity build: every feature evaluated twice (the first keeps the histogram)
+    // features [j0, j1) in steps of jstep are this wave's to evaluate one at a time
+    int j0 = wid, j1 = g, jstep = NW;
+    if constexpr (MODE == 1 && ESEG != 0) {
+      // binary Gini pre-filter path (what eval_feature would send to eval_gini_pf): the wave
+      // takes a contiguous share of the group (5 + 5 of a block-tier group of 10) and scores it
+      // NSEG features per pass, greedily; a pass is never padded, a last feature goes alone
+      const double* cwp = tree_cw<FC>(c, on.tree);
+      const double cw0 = cwk(cwp, 0), cw1 = cwk(cwp, 1);
+      if ((FC >= 0 || !c.mono) && gini_pf_ok(s, cw0, cw1)) {
+        const int per = (g + NW - 1) / NW;
+        int j = wid * per;
+        j1 = min(g, j + per);
+        jstep = 1;
+        if constexpr (ESEG == 4) {
+          for (; j + 4 <= j1; j += 4) {
+            eval_gini_seg<4, CT>(hist + j * span, s, lane, rg + j, rb + j, rn + j, rleft + j * c.CH, c.CH, true, cw0, cw1);
+            if (lane < 4) rmid[j + lane] = 0.0;
+          }
+        }
+        for (; j + 2 <= j1; j += 2) {
+          eval_gini_seg<2, CT>(hist + j * span, s, lane, rg + j, rb + j, rn + j, rleft + j * c.CH, c.CH, true, cw0, cw1);
+          if (lane < 2) rmid[j + lane] = 0.0;
+        }
+        j0 = j;
+      }
+    }
+    for (int j = j0; j < j1; j += jstep) {
+#ifdef DML_X2_EVAL  // sensitivity build: every feature evaluated twice (the first keeps the histogram)
       eval_feature<MODE, 3, CT>(hist + j * span, c.C, c.CH, s, lane, rg + j, rb + j, rn + j, rleft + j * c.CH, false,
                          tree_cw<FC>(c, on.tree), &c.rq, MonoQ{mono_of<FC>(c, s, feats[j]), sc->lo, sc->hi}, rmid + j);
       wave_lds_sync();
@@ -4431,6 +4633,48 @@ __global__ void k_test_pk16_sorts(const uint32_t* in, uint32_t* out) {
   o[3 * 64 + lane] = bitonic_seg_pk16<32>(v, lane);
 }
 
+// the segmented binary Gini evaluation against the one-feature routine
+// (tests/test_forest_eval_seg_gpu.py): one wave per block copies nfeat <= 8 histograms twice
+// into LDS, runs eval_gini_pf on every feature of the first copy and, on the second, the node
+// kernels' greedy grouping (fours if nseg = 4, then pairs, then a single).  Per block and set
+// (0 one-feature, 1 segmented): outd [8][4] = gain, left w0, left w1, left rows;
+// outi [8][3] = bin, nc, words of the copy left non-zero by zero_after
+constexpr int kEvalSegTestFeats = 8;
+template <class CT>
+__global__ __launch_bounds__(64) void k_test_eval_seg(const CT* in, int nfeat, int nseg, int msl, double mwl, double cw0,
+                                                      double cw1, double* outd, int* outi) {
+  constexpr int F = kEvalSegTestFeats;
+  __shared__ CT hh[2][F * 256];
+  __shared__ double rg[2][F], rleft[2][F * 3];
+  __shared__ int rb[2][F], rn[2][F];
+  const int lane = threadIdx.x;
+  const CT* src = in + (size_t)blockIdx.x * nfeat * 256;
+  for (int i = lane; i < nfeat * 256; i += 64) hh[0][i] = hh[1][i] = src[i];
+  __syncthreads();
+  NodeSpec s{};
+  s.criterion = kGini; s.min_samples_leaf = msl; s.min_weight_leaf = mwl;
+  for (int j = 0; j < nfeat; ++j)
+    eval_gini_pf<1, 1, CT>(hh[0] + j * 256, 256, s, lane, rg[0] + j, rb[0] + j, rn[0] + j, rleft[0] + 3 * j, 3, true, cw0, cw1);
+  int j = 0;
+  if (nseg == 4)
+    for (; j + 4 <= nfeat; j += 4)
+      eval_gini_seg<4, CT>(hh[1] + j * 256, s, lane, rg[1] + j, rb[1] + j, rn[1] + j, rleft[1] + 3 * j, 3, true, cw0, cw1);
+  for (; j + 2 <= nfeat; j += 2)
+    eval_gini_seg<2, CT>(hh[1] + j * 256, s, lane, rg[1] + j, rb[1] + j, rn[1] + j, rleft[1] + 3 * j, 3, true, cw0, cw1);
+  for (; j < nfeat; ++j)
+    eval_gini_pf<1, 1, CT>(hh[1] + j * 256, 256, s, lane, rg[1] + j, rb[1] + j, rn[1] + j, rleft[1] + 3 * j, 3, true, cw0, cw1);
+  __syncthreads();
+  for (int i = lane; i < 2 * nfeat; i += 64) {
+    const int set = i / nfeat, f = i % nfeat;
+    int left_nz = 0;
+    for (int b = 0; b < 256; ++b) left_nz += hh[set][f * 256 + b] != (CT)0 ? 1 : 0;
+    double* od = outd + (((size_t)blockIdx.x * 2 + set) * F + f) * 4;
+    int* oi = outi + (((size_t)blockIdx.x * 2 + set) * F + f) * 3;
+    od[0] = rg[set][f]; od[1] = rleft[set][3 * f]; od[2] = rleft[set][3 * f + 1]; od[3] = rleft[set][3 * f + 2];
+    oi[0] = rb[set][f]; oi[1] = rn[set][f]; oi[2] = left_nz;
+  }
+}
+
 struct PredictArgs;
 extern "C" int dml_forest_predict_fit(const PredictArgs* a, int32_t f, hipStream_t st);
 
@@ -4458,6 +4702,20 @@ int dml_test_pk16_sorts(const uint32_t* in, uint32_t* out, int64_t nblocks, hipS
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
+// word64: the histograms are u64 words (21/21/22), else the wave tier's u32 (12/12/8)
+int dml_test_eval_seg(const void* hist, int32_t word64, int32_t nfeat, int32_t nseg, int32_t min_samples_leaf,
+                      double min_weight_leaf, double cw0, double cw1, double* outd, int32_t* outi, int64_t nblocks,
+                      hipStream_t st) {
+  if (nfeat < 1 || nfeat > kEvalSegTestFeats || (nseg != 2 && nseg != 4) || nblocks < 1) return 2;
+  if (word64)
+    k_test_eval_seg<unsigned long long><<<(unsigned)nblocks, 64, 0, st>>>((const unsigned long long*)hist, nfeat, nseg,
+                                                                           min_samples_leaf, min_weight_leaf, cw0, cw1, outd, outi);
+  else
+    k_test_eval_seg<uint32_t><<<(unsigned)nblocks, 64, 0, st>>>((const uint32_t*)hist, nfeat, nseg, min_samples_leaf,
+                                                                 min_weight_leaf, cw0, cw1, outd, outi);
+  return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
 const char* dml_forest_last_error(int* line) {
   if (line) *line = g_last_err_line;
   return hipGetErrorString(g_last_err);
@@ -4471,6 +4729,8 @@ int dml_forest_large_stash() { return DML_LARGE_STASH != 0 ? 1 : 0; }
 int dml_forest_block_stash_planes() { return DML_BLOCK_STASH_PLANES != 0 ? 1 : 0; }
 // 1: binary subtrees sort two features per pass with packed 16-bit keys (DML_SUB_PK16)
 int dml_forest_sub_pk16() { return DML_SUB_PK16 != 0 ? 1 : 0; }
+// features the fused node kernels' binary Gini evaluation scores per wave pass (DML_EVAL_SEG: 0, 2 or 4)
+int dml_forest_eval_seg() { return DML_EVAL_SEG; }
 int dml_forest_sizeof_treespec() { return (int)sizeof(TreeSpec); }
 int dml_forest_sizeof_args() { return (int)sizeof(ForestArgs); }
 int dml_forest_sizeof_node() { return (int)sizeof(NodeRec); }

@@ -350,6 +350,9 @@ def _register_optional(lib) -> None:
         "dml_forest_release_scratch": (c_i32, []),
         "dml_forest_block_stash_planes": (c_i32, []),
         "dml_forest_sub_pk16": (c_i32, []),
+        "dml_forest_eval_seg": (c_i32, []),
+        "dml_test_eval_seg": (c_i32, [c_vp, c_i32, c_i32, c_i32, c_i32, ctypes.c_double, ctypes.c_double,
+                                      ctypes.c_double, c_vp, c_vp, c_i64, c_vp]),
         "dml_mae_sizeof_args": (c_i32, []),
         "dml_mae_sizeof_open": (c_i32, []),
         "dml_mae_sizeof_res": (c_i32, []),
