@@ -114,6 +114,12 @@ def _run(cmd: list[str]) -> None:
         raise RuntimeError(f"build failed: {' '.join(cmd)}")
 
 
+# Flags of single units, on top of the common ones (they enter the unit's and the library's
+# content hash).  neighbors_wide.hip is built without packed fp32 instructions (v_pk_fma_f32
+# and kin): its distance chains are plain per-lane fma / add chains, as ``k_knn``'s source is.
+UNIT_FLAGS = {"neighbors_wide.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def build_hip(force: bool = False, out: str = HIP_LIB, extra_flags: tuple = ()) -> str:
     """``out`` / ``extra_flags``: A/B variants of the kernel library (e.g. ``-DDML_PHASE_PROF``
     into ``lib/libdml_hip_phase.so``, loaded through ``DML_HIP_LIB``)."""
@@ -122,16 +128,17 @@ def build_hip(force: bool = False, out: str = HIP_LIB, extra_flags: tuple = ()) 
     os.makedirs(LIB, exist_ok=True)
     flags = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result",
              "-I", os.path.join(CSRC, "kernels"), *extra_flags]
+    hflags = flags + [f"{u}: {' '.join(f)}" for u, f in sorted(UNIT_FLAGS.items())]
     # staleness by CONTENT (sources + headers + flags), never by mtime: the .so files are
     # git-ignored but travel with the tree to the GPU box, where every file has a fresh
     # mtime -- an mtime test there could keep a library that does not match the sources
     with _BuildLock():
-        if force or _stale_by_hash(out, srcs + hdrs, flags):
-            _build_hip_locked(out, srcs, hdrs, flags, force)
+        if force or _stale_by_hash(out, srcs + hdrs, hflags):
+            _build_hip_locked(out, srcs, hdrs, flags, hflags, force)
     return out
 
 
-def _build_hip_locked(out, srcs, hdrs, flags, force) -> None:
+def _build_hip_locked(out, srcs, hdrs, flags, hflags, force) -> None:
     # one hipcc per translation unit, in parallel (forest.hip alone is most of the
     # build), then one link; a unit whose own content hash is unchanged keeps its object
     from concurrent.futures import ThreadPoolExecutor
@@ -142,16 +149,17 @@ def _build_hip_locked(out, srcs, hdrs, flags, force) -> None:
 
     def compile_one(so):
         src, obj = so
-        if force or _stale_by_hash(obj, [src] + hdrs, flags):
-            _run([_hipcc(), *flags, "-c", src, "-o", obj])
-            _stamp(obj, [src] + hdrs, flags)
+        uflags = flags + UNIT_FLAGS.get(os.path.basename(src), [])
+        if force or _stale_by_hash(obj, [src] + hdrs, uflags):
+            _run([_hipcc(), *uflags, "-c", src, "-o", obj])
+            _stamp(obj, [src] + hdrs, uflags)
 
     with ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
         list(ex.map(compile_one, zip(srcs, objs)))
     tmp = _tmp(out)
     _run([_hipcc(), f"--offload-arch={ARCH}", "-shared", *objs, "-o", tmp])
     os.replace(tmp, out)
-    _stamp(out, srcs + hdrs, flags)
+    _stamp(out, srcs + hdrs, hflags)
 
 
 def build_cpu(force: bool = False) -> str:

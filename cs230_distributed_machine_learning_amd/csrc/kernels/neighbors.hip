@@ -20,16 +20,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "knn_common.h"
 #include "wave_ops.h"
 
 namespace {
 
+using dml::knn::accum;
+using dml::knn::kInf;
+using dml::knn::QPW;             // queries per wave
 using dml::wave::lane_id;
 using dml::wave::shfl_xor;
 
-constexpr int QPW = 8;           // queries per wave
 constexpr int WAVES = 4;         // waves per block
-constexpr uint64_t kInf = ~0ull;
 
 template <int K, int J>
 __device__ __forceinline__ uint64_t bstep(uint64_t key, int lane) {
@@ -66,15 +68,6 @@ __device__ __forceinline__ uint64_t merge_top(uint64_t top, uint64_t cand, int l
   const uint64_t desc = ~sort64(~cand, lane);           // candidates sorted descending
   const uint64_t m = top < desc ? top : desc;           // bitonic, holds the 64 smallest
   return merge64(m, lane);
-}
-
-template <int METRIC>
-__device__ __forceinline__ float accum(float acc, float x, float q, float p) {
-  const float t = x - q;
-  if constexpr (METRIC == 0) return __builtin_fmaf(t, t, acc);   // squared L2
-  if constexpr (METRIC == 1) return acc + __builtin_fabsf(t);     // L1
-  if constexpr (METRIC == 2) return __builtin_fmaxf(acc, __builtin_fabsf(t));   // Linf
-  return acc + __powf(__builtin_fabsf(t), p);                     // general Minkowski (p-th power sum)
 }
 
 template <int METRIC>
@@ -115,7 +108,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_knn(const float* __restrict__ X,
     }
 #pragma unroll
     for (int i = 0; i < QPW; ++i) {
-      const uint64_t key = valid ? (((uint64_t)__builtin_bit_cast(uint32_t, acc[i]) << 32) | (uint32_t)j) : kInf;
+      const uint64_t key = valid ? dml::knn::make_key(dml::knn::key_distance<METRIC>(acc[i]), j) : kInf;
       const uint64_t thr = dml::wave::bcast(top[i], K - 1);
       if (__builtin_amdgcn_ballot_w64(key < thr) != 0) top[i] = merge_top(top[i], key, lane);
     }
@@ -324,7 +317,8 @@ __global__ __launch_bounds__(256) void k_knn_l2_mfma(const __bf16* __restrict__ 
 }  // namespace
 
 // qrow/qsplit: [nq_groups * 8] (qrow -1 = padding); out_d/out_i: [nq_groups * 8, K], K <= 64.
-// metric: 0 squared-L2, 1 L1, 2 Linf, 3 sum |t|^p.
+// metric: 0 squared-L2, 1 L1, 2 Linf, 3 sum |t|^p, 4 cosine (X / XT are then the unit rows and
+// their feature-major copy; out_d holds clip(1 - dot, 0, 2)).
 extern "C" int dml_knn(const float* X, const float* XT, int64_t n, int64_t d, const uint8_t* roles,
                        const int32_t* qrow, const int32_t* qsplit, int64_t nq_groups, int32_t metric, float p,
                        int32_t K, float* out_d, int32_t* out_i, hipStream_t st) {
@@ -334,6 +328,7 @@ extern "C" int dml_knn(const float* X, const float* XT, int64_t n, int64_t d, co
     case 0: k_knn<0><<<blocks, 64 * WAVES, 0, st>>>(X, XT, n, d, roles, qrow, qsplit, nq_groups, p, K, out_d, out_i); break;
     case 1: k_knn<1><<<blocks, 64 * WAVES, 0, st>>>(X, XT, n, d, roles, qrow, qsplit, nq_groups, p, K, out_d, out_i); break;
     case 2: k_knn<2><<<blocks, 64 * WAVES, 0, st>>>(X, XT, n, d, roles, qrow, qsplit, nq_groups, p, K, out_d, out_i); break;
+    case 4: k_knn<4><<<blocks, 64 * WAVES, 0, st>>>(X, XT, n, d, roles, qrow, qsplit, nq_groups, p, K, out_d, out_i); break;
     default: k_knn<3><<<blocks, 64 * WAVES, 0, st>>>(X, XT, n, d, roles, qrow, qsplit, nq_groups, p, K, out_d, out_i); break;
   }
   return hipGetLastError() == hipSuccess ? 0 : 1;

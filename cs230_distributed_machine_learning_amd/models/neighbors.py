@@ -5,13 +5,16 @@ predicts them once per (candidate, fold): a KD/ball tree build plus a query pass
 time (sklearn ``neighbors/_kd_tree``, ``_ball_tree``, ``_pairwise_distances_reduction``).
 
 Here a KNN "fit" is only the choice of training rows (a role row of the split tensor),
-so for every metric the job uses ONE exact brute-force pass (HIP kernel ``dml_knn``,
-csrc/kernels/neighbors.hip; torch on CPU) finds the ``K_max`` nearest training rows of
+so for every metric the job uses ONE exact brute-force pass (HIP kernels ``dml_knn``,
+csrc/kernels/neighbors.hip, for K_max <= 64 and ``dml_knn_wide``,
+csrc/kernels/neighbors_wide.hip, up to 512; torch on CPU and above 512) finds the
+``K_max`` nearest training rows of
 every test row of every split; each candidate (n_neighbors, weights) then votes from a
 prefix of those lists.  Neighbour search is exact, so predictions match sklearn's
 brute/kd/ball algorithms except where equal distances make the k-th neighbour
 ambiguous (ties resolved by lower row index here; parity unpinned for exact ties).
-``metric="cosine"`` is a library GEMM over unit rows (sklearn's cosine_distances).
+``metric="cosine"`` ranks by ``clip(1 - <u_q, u_r>, 0, 2)`` over unit rows (sklearn's
+cosine_distances): the same kernels on ``unit_operands`` on the GPU, a library GEMM on CPU.
 ``algorithm`` / ``leaf_size`` only pick sklearn's search structure and are accepted
 and ignored.
 """
@@ -31,7 +34,8 @@ from .base import Family, FitOutput, FitTask, ParamError, as_int, as_float, regi
 _DEFAULTS = {"n_neighbors": 5, "weights": "uniform", "algorithm": "auto", "leaf_size": 30, "p": 2,
              "metric": "minkowski", "metric_params": None, "n_jobs": None}
 M_L2, M_L1, M_LINF, M_P, M_COS = 0, 1, 2, 3, 4
-KERNEL_KMAX = 64
+KERNEL_KMAX = 64    # ``dml_knn``: a query's top list is one key per lane of a wave
+WIDE_KMAX = 512     # ``dml_knn_wide``: top lists in LDS
 
 _METRICS = {"euclidean": (M_L2, 2.0), "l2": (M_L2, 2.0), "manhattan": (M_L1, 1.0), "cityblock": (M_L1, 1.0),
             "l1": (M_L1, 1.0), "chebyshev": (M_LINF, math.inf), "infinity": (M_LINF, math.inf),
@@ -106,9 +110,35 @@ def knn_search_torch(X: torch.Tensor, qrows: torch.Tensor, train_rows: torch.Ten
 
 MFMA_KMAX = 32   # largest K the host sends to the matrix-core path (it re-ranks 64 candidates)
 
-# counts of the last ``knn_search_hip`` call: queries searched on the matrix cores, and how
-# many of them the kernel could not certify and the scalar kernel searched again
-last_search_stats = {"mfma_queries": 0, "fallback_queries": 0}
+# counts of the last ``knn_search_hip`` call: queries searched on the matrix cores, how many
+# of them the kernel could not certify and the scalar kernel searched again, and queries
+# searched by the wide kernel (``dml_knn_wide``)
+last_search_stats = {"mfma_queries": 0, "fallback_queries": 0, "wide_queries": 0}
+
+
+def _wide_mode() -> str:
+    """``DML_KNN_WIDE``: ``auto`` (default) sends 64 < K <= 512 to ``dml_knn_wide``, ``1`` every
+    K <= 512 (to compare it with ``dml_knn``), ``0`` none (K > 64 takes the torch search)."""
+    return os.environ.get("DML_KNN_WIDE", "auto")
+
+
+def hip_search_serves(K: int) -> bool:
+    """Whether ``knn_search_hip`` has a kernel for this K (any metric)."""
+    return K <= (KERNEL_KMAX if _wide_mode() == "0" else WIDE_KMAX)
+
+
+def unit_operands(data):
+    """Operands of the cosine metric, built once per table: the unit rows
+    ``U = float32(X.double() / |x|)`` (zero rows stay zero: sklearn's ``normalize``) and
+    their feature-major copy ``UT``.  The kernels rank by ``clip(1 - <u_q, u_r>, 0, 2)``."""
+    ops = getattr(data, "_knn_unit_ops", None)
+    if ops is None:
+        Xd = data.X.double()
+        nrm = torch.linalg.vector_norm(Xd, dim=1, keepdim=True)
+        U = (Xd / torch.where(nrm > 0, nrm, torch.ones_like(nrm))).float().contiguous()
+        ops = (U, U.t().contiguous())
+        data._knn_unit_ops = ops
+    return ops
 
 
 def mfma_error_consts(ks: int) -> Tuple[float, float]:
@@ -158,16 +188,23 @@ def mfma_operands(data):
 
 def knn_search_hip(data, splits: List[int], K: int, metric: int, p: float) -> Dict[int, Tuple[torch.Tensor, torch.Tensor]]:
     """One kernel launch for all test rows of all ``splits``: squared L2 with K <= 32 on the
-    matrix cores, every other metric on the scalar streaming kernel.  The matrix-core kernel
+    matrix cores, every other metric and K <= 64 on the scalar streaming kernel, 64 < K <= 512
+    (``DML_KNN_WIDE=1``: every K) on the wide kernel, which computes the scalar kernel's
+    accumulators.  Cosine runs the same kernels on ``unit_operands``.  The matrix-core kernel
     re-ranks an approximately selected top-64 exactly and flags every query for which it
     cannot prove that selection sufficient; flagged queries are searched again by the scalar
     kernel, so the result is the scalar kernel's, bit for bit, on any data
     (``last_search_stats`` counts both)."""
+    if not hip_search_serves(K):
+        raise ValueError(f"no HIP neighbour search for K = {K} (DML_KNN_WIDE={_wide_mode()})")
     lib = native.hip_lib()
     qpw = int(lib.dml_knn_qpw())
     dev = data.device
-    use_mfma = metric == M_L2 and K <= MFMA_KMAX and os.environ.get("DML_KNN_MFMA", "1") != "0"
-    last_search_stats.update(mfma_queries=0, fallback_queries=0)
+    use_wide = K > KERNEL_KMAX or _wide_mode() == "1"
+    use_mfma = (metric == M_L2 and K <= MFMA_KMAX and not use_wide
+                and os.environ.get("DML_KNN_MFMA", "1") != "0")
+    last_search_stats.update(mfma_queries=0, fallback_queries=0, wide_queries=0)
+    Xk, XTk = unit_operands(data) if metric == M_COS else (data.X, data.feature_major())
     qr, qs, spans = [], [], {}
     off = 0
     for s in splits:
@@ -188,12 +225,13 @@ def knn_search_hip(data, splits: List[int], K: int, metric: int, p: float) -> Di
     out_d = torch.empty((qrow.numel(), K), dtype=torch.float32, device=dev)
     out_i = torch.empty((qrow.numel(), K), dtype=torch.int32, device=dev)
     def scalar(qrow, qsplit, out_d, out_i):
-        rc = lib.dml_knn(native.ptr(data.X), native.ptr(data.feature_major()), data.n, data.d, native.ptr(data.roles),
-                         native.ptr(qrow), native.ptr(qsplit), qrow.numel() // qpw, metric,
-                         float(p if math.isfinite(p) else 0.0), K, native.ptr(out_d), native.ptr(out_i),
-                         native.stream_handle(dev))
+        name = "dml_knn_wide" if use_wide else "dml_knn"
+        rc = getattr(lib, name)(native.ptr(Xk), native.ptr(XTk), data.n, data.d, native.ptr(data.roles),
+                                native.ptr(qrow), native.ptr(qsplit), qrow.numel() // qpw, metric,
+                                float(p if math.isfinite(p) else 0.0), K, native.ptr(out_d), native.ptr(out_i),
+                                native.stream_handle(dev))
         if rc:
-            raise RuntimeError(f"dml_knn failed (rc={rc})")
+            raise RuntimeError(f"{name} failed (rc={rc})")
 
     if use_mfma:
         xhl, npad, ks, rn, rmax, c1, c2 = mfma_operands(data)
@@ -217,6 +255,8 @@ def knn_search_hip(data, splits: List[int], K: int, metric: int, p: float) -> Di
             out_i.view(groups, qpw, K)[redo] = fi.view(-1, qpw, K)
     else:
         scalar(qrow, qsplit, out_d, out_i)
+        if use_wide:
+            last_search_stats["wide_queries"] = int(sum(m for _, m in spans.values()))
     return {s: (out_d[o:o + m], out_i[o:o + m].long()) for s, (o, m) in spans.items()}
 
 
@@ -291,7 +331,7 @@ def knn_search_sharded(data, splits: List[int], K: int, metric: int, p: float, y
     Qs = {s: data._gather_rows(data.X[data.test_rows[s].long()], data._test_counts[s]) for s in splits}
     hip = None
     # the HIP search (MFMA for L2) needs K candidates on this rank for every split
-    if (data.is_gpu and K <= KERNEL_KMAX and metric != M_COS
+    if (data.is_gpu and hip_search_serves(K)
             and all(int(data.train_rows[s].numel()) >= K for s in splits)):
         hip = knn_search_hip(_QueryTable(data, Qs), splits, K, metric, p)
     for s in splits:
@@ -384,7 +424,7 @@ def knn_search_streamed(data, splits: List[int], K: int, metric: int, p: float, 
         for r0, r1, Xc in data.stream_rows():
             tab = _ChunkTable(data, r0, Xc, Q, qpos)
             enough = all(int((tab.roles[s, :r1 - r0] == 1).sum()) >= K for s in qpos)
-            if data.is_gpu and K <= KERNEL_KMAX and metric != M_COS and enough:
+            if data.is_gpu and hip_search_serves(K) and enough:
                 got = knn_search_hip(tab, sorted(qpos), K, metric, p)
                 cd = torch.cat([got[s][0].float() for s, _, _ in block])
                 ci = torch.cat([got[s][1] for s, _, _ in block]) + r0
@@ -463,7 +503,7 @@ class KNeighborsFamily(Family):
                 nb = knn_search_sharded(data, splits, kmax, metric, p, y)
             elif data.X is None and getattr(data, "can_stream_rows", lambda: False)():
                 nb = knn_search_streamed(data, splits, kmax, metric, p, y)
-            elif data.is_gpu and kmax <= KERNEL_KMAX and metric != M_COS:
+            elif data.is_gpu and hip_search_serves(kmax):
                 nb = {s: (a, y[i]) for s, (a, i) in knn_search_hip(data, splits, kmax, metric, p).items()}
             else:
                 nb = {s: (a, y[i]) for s, (a, i) in ((s, knn_search_torch(data.X, data.test_rows[s], data.train_rows[s],
