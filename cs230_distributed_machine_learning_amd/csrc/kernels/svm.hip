@@ -19,6 +19,7 @@
 #include <stdint.h>
 #include <math.h>
 
+#include "svm_args.h"
 #include "wave_ops.h"
 
 namespace {
@@ -28,25 +29,11 @@ constexpr int kMaxLdsD = 2048;   // query rows up to this many features are stag
 constexpr double kTau = 1e-12;
 constexpr double kInf = 1e300;
 
-enum { KLIN = 0, KPOLY = 1, KRBF = 2, KSIG = 3 };
-
-// host-shared problem record: every field 8 bytes
-struct SvmProb {
-  int64_t xoff;      // feature-major rows of this problem's rowset: X[xoff + f * nrows + r]
-  int64_t roff;      // per-row arrays (qd): qd[roff + r]
-  int64_t nrows;     // rows in the rowset
-  int64_t L;         // dual variables (nrows for SVC, 2 nrows for epsilon-SVR)
-  int64_t voff;      // per-variable arrays: y, C, alpha, G at [voff, voff + L)
-  int64_t koff;      // kernel-column scratch: 2 * nrows floats at koff
-  int64_t kernel, degree;
-  double gamma, coef0, eps;
-  int64_t max_iter;  // total iteration budget
-  int64_t iters;     // in/out: iterations done so far
-  int64_t status;    // in/out: 0 running, 1 optimal, 2 iteration limit
-  int64_t svr;       // 1: variable t uses row t mod nrows
-  int64_t coff;      // split solver: kernel-column cache, S * nrows floats at coff
-  int64_t moff;      // split solver: per-workgroup cache maps, B * (nrows + 2 S) ints at moff
-};
+using dml::KLIN;
+using dml::KPOLY;
+using dml::KRBF;
+using dml::KSIG;
+using dml::SvmProb;   // host-shared problem record (svm_args.h): every field 8 bytes
 
 __device__ __forceinline__ float kfun(int kernel, double gamma, double coef0, int degree, float acc) {
   switch (kernel) {

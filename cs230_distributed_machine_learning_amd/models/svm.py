@@ -8,8 +8,18 @@ Here each (candidate, split[, class pair]) is one dual problem for the batched s
 libsvm's algorithm (WSS3 selection, same update / stopping rule / tie rules), so the
 support vectors and decision values match libsvm up to float round-off in the kernel
 values.  Rows of each (split, class pair) are gathered ONCE into a feature-major block
-shared by every candidate using it.  Decision values for held-out rows are kernel
-matrix x coefficient products (library GEMM).  Supported: C, kernel
+shared by every candidate using it.  The step after the solve is batched the same way
+(``svm_decisions``, csrc/kernels/svm_decision.hip, docs/SVM_DECISION.md): rho and the
+support-vector compaction of every problem in one launch, the decision values of every
+problem's held-out rows in a second (float64, the direct kernel formula against the
+feature-major rowset blocks; an inner Platt problem writes straight into its machine's
+held-out vector) and the one-vs-one votes in a third, with nothing read back unless models
+are kept.  ``DML_SVM_DECISION`` = ``auto`` (default: that path on a GPU device, the per-problem
+torch loop -- kernel matrix x coefficient products through a library GEMM -- on a CPU
+device), ``1`` (the batched path on any device: the host twins on a CPU one) or ``0`` (the
+loop).  ``last_decision_stats`` reports problems, queries, launches and host reads of the
+last run (with ``DML_SVM_DECISION_PAIRS=1`` also the (query, support vector) pairs, which costs
+one read).  Supported: C, kernel
 (linear/poly/rbf/sigmoid), degree, gamma ('scale'/'auto'/float), coef0, tol, max_iter,
 class_weight (dict / 'balanced'), epsilon (SVR).  ``shrinking`` / ``cache_size`` only
 affect libsvm's speed and are accepted and ignored; ``break_ties=True`` predicts the argmax of
@@ -57,6 +67,7 @@ SPLIT_CHUNK_ITERS = 50000
 CACHE_FRACTION = 0.25        # of free HBM for the kernel-column caches (libsvm cache_size analogue) ...
 CACHE_MAX_GB = 48.0          # ... and at most this much (DML_SVM_CACHE_GB; 288 GB of HBM per MI355X)
 MIN_ROWS_PER_WG = 1024       # split a problem over workgroups only down to this slice size
+DEC_QUERY_TILE = 8           # query rows per workgroup of k_svm_decision (csrc/kernels/svm_args.h kSvmDecQT)
 
 # ---- SVC(probability=True): libsvm's Platt scaling + pairwise coupling (docs/SVC_PROBABILITY.md) ----
 PLATT_FOLDS = 5              # libsvm's inner cross-validation
@@ -197,6 +208,7 @@ class SVMFamily(Family):
         # ---- Platt scaling: the four-fifths rowsets of the inner 5-fold CV, gathered once per
         # (split, pair, seed); held[key] = the held-out fifths as positions in the machine's rows
         held: Dict[Tuple, List[torch.Tensor]] = {}
+        held_pos: Dict[Tuple, List[np.ndarray]] = {}   # the same positions on the host (svm_decisions)
         for ti, t in enumerate(tasks):
             if not wants[ti]:
                 continue
@@ -208,6 +220,7 @@ class SVMFamily(Family):
                     continue
                 folds = platt_folds(rows.numel(), sd)
                 held[key] = [torch.from_numpy(f).to(dev) for f in folds]
+                held_pos[key] = folds
                 for f, ho in enumerate(folds):
                     rest = np.setdiff1d(np.arange(rows.numel()), ho)   # ascending: the rows keep their order
                     rowsets[key + (f,)] = rows[torch.from_numpy(rest).to(dev)]
@@ -272,9 +285,67 @@ class SVMFamily(Family):
         a_all = torch.zeros_like(G_all)
         self._solve(data, P, Xrs, y_all, C_all, qd_all, a_all, G_all, koff)
         # ---- rho, decision values, predictions --------------------------------------------
+        mode = os.environ.get("DML_SVM_DECISION", "auto")
+        if mode not in ("auto", "1", "0"):
+            raise ValueError(f"DML_SVM_DECISION={mode!r} (auto / 1 / 0)")
+        preds: Dict[int, torch.Tensor] = {}
+        if mode == "1" or (mode == "auto" and data.is_gpu):
+            dec, cvdec, preds, models = svm_decisions(self, data, tasks, pairs, P, prob_of, rowsets, held_pos,
+                                                      const_dec, Xrs, y_all, C_all, a_all, G_all, keep_models)
+        else:
+            dec, cvdec, models = self._decisions_loop(data, tasks, pairs, P, prob_of, rowsets, held, const_dec,
+                                                      y_all, C_all, a_all, G_all, keep_models)
+        for k in np.nonzero(P["status"] == 2)[0]:
+            t = tasks[prob_of[k][0]]
+            w = f"Solver terminated early (max_iter={int(P[k]['max_iter'])})"
+            if w not in t.params["warnings"]:
+                t.params["warnings"].append(w)
+        proba = self._probabilities(data, tasks, wants, pairs, rowsets, dec, cvdec, models)
+        data.sync()
+        dt = time.perf_counter() - t0
+        outs = []
+        for ti, t in enumerate(tasks):
+            te = data.test_rows[t.split]
+            if svr:
+                pred = dec[(ti, 0)].float() if (ti, 0) in dec else torch.zeros(te.numel(), device=dev)
+            elif ti in preds and not (t.params.get("break_ties") and C_cls > 2):
+                pred = preds[ti]                            # k_svm_vote
+            else:
+                votes = torch.zeros((te.numel(), C_cls), dtype=torch.int32, device=dev)
+                for pi, (a_, b_) in enumerate(pairs):
+                    dv = dec.get((ti, pi))
+                    if dv is None:
+                        continue
+                    votes[:, a_] += (dv > 0).int()
+                    votes[:, b_] += (dv <= 0).int()
+                pred = votes.argmax(1).to(torch.int32)      # first max = lowest class (libsvm vote)
+                if t.params.get("break_ties") and C_cls > 2:
+                    pred = _ovr_argmax(dec, ti, pairs, te.numel(), C_cls, dev)
+            o = FitOutput(task_id=t.task_id, pred=pred, fit_seconds=dt / len(tasks),
+                          info={"warnings": t.params["warnings"]})
+            if not svr and C_cls == 2 and (ti, 0) in dec:
+                o.decision = -dec[(ti, 0)]   # sklearn's binary decision_function: positive -> classes_[1]
+            if wants[ti] and _asks_proba(t):
+                o.proba = proba[ti]
+            if keep_models:
+                rp = t.params
+                o.model = {"kind": "svm", "svr": svr, "machines": models.get(ti, []), "kernel": rp["kernel"],
+                           "gamma": float(self._gamma(data, t, rp["gamma"], {})), "coef0": rp["coef0"],
+                           "degree": rp["degree"], "n_classes": C_cls,
+                           "classes": None if svr else np.asarray(data.classes).tolist(), "model_type": t.model_type}
+                if wants[ti]:
+                    o.model["probability"] = True
+            outs.append(o)
+        return outs
+
+    def _decisions_loop(self, data, tasks, pairs, P, prob_of, rowsets, held, const_dec, y_all, C_all, a_all, G_all,
+                        keep_models):
+        """``DML_SVM_DECISION=0`` (and ``auto`` on a CPU device): one dual problem at a time in torch --
+        rho, the support-vector gather, a kernel matrix x coefficient product (library GEMM)."""
         dec: Dict[Tuple[int, int], torch.Tensor] = {}
         cvdec: Dict[Tuple[int, int], torch.Tensor] = {}   # Platt: held-out values in the machine's row order
         models: Dict[int, list] = {}
+        dev, svr, queries = data.device, not data.classification, 0
         for k, (ti, pi, key, fold) in enumerate(prob_of):
             t = tasks[ti]
             rec = P[k]
@@ -306,10 +377,7 @@ class SVMFamily(Family):
                 if keep_models:
                     models.setdefault(ti, []).append({"sv": Xsv.cpu().numpy(), "coef": coef[sv].cpu().numpy(),
                                                       "rho": float(rho), "pair": pairs[pi]})
-            if int(rec["status"]) == 2:
-                w = f"Solver terminated early (max_iter={int(rec['max_iter'])})"
-                if w not in t.params["warnings"]:
-                    t.params["warnings"].append(w)
+            queries += int(te.numel())
         for (ti, pi, fold), v in const_dec.items():
             t, pr = tasks[ti], pairs[pi]
             mrows = rowsets[(t.split, pr)]
@@ -317,41 +385,9 @@ class SVMFamily(Family):
             if (ti, pi) not in cvdec:
                 cvdec[(ti, pi)] = torch.zeros(mrows.numel(), dtype=torch.float64, device=dev)
             cvdec[(ti, pi)][held[(t.split, pr, sd)][fold]] = v
-        proba = self._probabilities(data, tasks, wants, pairs, rowsets, dec, cvdec, models)
-        data.sync()
-        dt = time.perf_counter() - t0
-        outs = []
-        for ti, t in enumerate(tasks):
-            te = data.test_rows[t.split]
-            if svr:
-                pred = dec[(ti, 0)].float() if (ti, 0) in dec else torch.zeros(te.numel(), device=dev)
-            else:
-                votes = torch.zeros((te.numel(), C_cls), dtype=torch.int32, device=dev)
-                for pi, (a_, b_) in enumerate(pairs):
-                    dv = dec.get((ti, pi))
-                    if dv is None:
-                        continue
-                    votes[:, a_] += (dv > 0).int()
-                    votes[:, b_] += (dv <= 0).int()
-                pred = votes.argmax(1).to(torch.int32)      # first max = lowest class (libsvm vote)
-                if t.params.get("break_ties") and C_cls > 2:
-                    pred = _ovr_argmax(dec, ti, pairs, te.numel(), C_cls, dev)
-            o = FitOutput(task_id=t.task_id, pred=pred, fit_seconds=dt / len(tasks),
-                          info={"warnings": t.params["warnings"]})
-            if not svr and C_cls == 2 and (ti, 0) in dec:
-                o.decision = -dec[(ti, 0)]   # sklearn's binary decision_function: positive -> classes_[1]
-            if wants[ti] and _asks_proba(t):
-                o.proba = proba[ti]
-            if keep_models:
-                rp = t.params
-                o.model = {"kind": "svm", "svr": svr, "machines": models.get(ti, []), "kernel": rp["kernel"],
-                           "gamma": float(self._gamma(data, t, rp["gamma"], {})), "coef0": rp["coef0"],
-                           "degree": rp["degree"], "n_classes": C_cls,
-                           "classes": None if svr else np.asarray(data.classes).tolist(), "model_type": t.model_type}
-                if wants[ti]:
-                    o.model["probability"] = True
-            outs.append(o)
-        return outs
+        self.last_decision_stats = {"path": "torch loop", "problems": len(prob_of), "queries": queries,
+                                    "launches": None, "host_reads": None}
+        return dec, cvdec, models
 
     def _probabilities(self, data, tasks, wants, pairs, rowsets, dec, cvdec, models) -> Dict[int, torch.Tensor]:
         """Platt scaling + pairwise coupling of the fits in ``wants``: ONE sigmoid-fit launch
@@ -600,6 +636,154 @@ def _rho(a, g, y, C) -> float:
     ub = float(yG[ub_mask].min()) if bool(ub_mask.any()) else math.inf
     lb = float(yG[lb_mask].max()) if bool(lb_mask.any()) else -math.inf
     return (ub + lb) / 2
+
+
+def _native_call(data, name: str, args) -> None:
+    """One launch of csrc/kernels/svm_decision.hip on a GPU device, its host twin
+    (csrc/runtime/svm_cpu.cpp) on a CPU one.  A missing kernel is an error."""
+    if data.is_gpu:
+        fn = getattr(native.hip_lib(), "dml_svm_" + name, None)
+        if fn is None:
+            raise RuntimeError(f"dml_svm_{name} is missing from the HIP kernel library (stale build?)")
+        rc = fn(ctypes.byref(args), native.stream_handle(data.device))
+    else:
+        rc = getattr(native.cpu_lib(), "dml_cpu_svm_" + name)(ctypes.byref(args))
+    if rc:
+        raise RuntimeError(f"dml_svm_{name} failed ({rc})")
+
+
+def svm_decisions(fam, data, tasks, pairs, P, prob_of, rowsets, held_pos, const_dec, Xrs, y, C, alpha, G,
+                  keep_models):
+    """The post-solve phase of every dual problem of the job in three launches
+    (csrc/kernels/svm_decision.hip; docs/SVM_DECISION.md): rho + support-vector compaction,
+    decision values, votes.  Everything the launches need (query rows, output slots, work list)
+    is built on the host from sizes it already knows, so nothing is read back unless models are
+    kept -- then rho, the compacted indices and the coefficients come back once for the batch.
+
+    Returns ``dec[(ti, pi)]`` (an outer problem's test-row values), ``cvdec[(ti, pi)]`` (a
+    machine's inner-fold values in its row order: each inner problem writes its held-out fifth
+    in place), ``pred[ti]`` (the vote; SVC only) -- all views of one float64 / int32 buffer --
+    and the kept ``machines`` per task."""
+    dev, svr, nprob = data.device, not data.classification, len(prob_of)
+    to_dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)   # noqa: E731
+    # ---- query rows and output slots: host arithmetic on known sizes -----------------------
+    pool, pool_off = [], {}          # device row lists the queries are drawn from, each once
+
+    def source(key, rows) -> int:
+        if key not in pool_off:
+            pool_off[key] = sum(r.numel() for r in pool)
+            pool.append(rows.long())
+        return pool_off[key]
+
+    dec_off: Dict[Tuple[int, int], Tuple[int, int]] = {}
+    cv_off: Dict[Tuple[int, int], Tuple[int, int]] = {}
+    total = 0
+
+    def cv_slot(ti, pi) -> int:
+        nonlocal total
+        if (ti, pi) not in cv_off:
+            cv_off[(ti, pi)] = (total, int(rowsets[(tasks[ti].split, pairs[pi])].numel()))
+            total += cv_off[(ti, pi)][1]
+        return cv_off[(ti, pi)][0]
+
+    qsrc, opos, qinfo, qtot = [], [], np.zeros((nprob, 2), dtype=np.int64), 0
+    ar: Dict[int, np.ndarray] = {}
+    for k, (ti, pi, key, fold) in enumerate(prob_of):
+        t = tasks[ti]
+        if fold < 0:
+            m = int(data.test_rows[t.split].numel())
+            span = ar.setdefault(m, np.arange(m, dtype=np.int64))
+            src, pos = source(("test", t.split), data.test_rows[t.split]) + span, total + span
+            dec_off[(ti, pi)] = (total, m)
+            total += m
+            if keep_models:
+                source(("rows", key), rowsets[key])
+        else:
+            ho = held_pos[key[:3]][fold].astype(np.int64)
+            src, pos = source(("rows", key[:2]), rowsets[key[:2]]) + ho, cv_slot(ti, pi) + ho
+        qinfo[k] = (qtot, src.size)
+        qtot += src.size
+        qsrc.append(src)
+        opos.append(pos)
+    const_pos, const_val = [], []    # inner folds with one class left: libsvm's constant, no problem
+    for (ti, pi, fold), v in const_dec.items():
+        t = tasks[ti]
+        ho = held_pos[(t.split, pairs[pi], _task_platt_seed(t, pi))][fold].astype(np.int64)
+        const_pos.append(cv_slot(ti, pi) + ho)
+        const_val.append(np.full(ho.size, v))
+    out = torch.zeros(max(1, total), dtype=torch.float64, device=dev)
+    if const_pos:
+        out[to_dev(np.concatenate(const_pos))] = to_dev(np.concatenate(const_val))
+    # ---- work list: (problem, query tile), the problems with the most rows first -----------
+    ntile = (qinfo[:, 1] + DEC_QUERY_TILE - 1) // DEC_QUERY_TILE
+    first = np.cumsum(ntile) - ntile
+    work = np.empty((int(ntile.sum()), 2), dtype=np.int32)
+    work[:, 0] = np.repeat(np.arange(nprob), ntile)
+    work[:, 1] = np.arange(work.shape[0]) - np.repeat(first, ntile)
+    work = work[np.argsort(-P["nrows"][work[:, 0]], kind="stable")]
+    # ---- launches ----------------------------------------------------------------------------
+    if data.is_gpu and native.hip_lib().dml_svm_dec_query_tile() != DEC_QUERY_TILE:
+        raise RuntimeError("query tile mismatch between the HIP kernel library and Python")
+    nrows_sum = int(P["nrows"].sum())
+    Pd = torch.from_numpy(P.view(np.uint8).copy()).to(dev)
+    sv_idx = torch.zeros(max(1, nrows_sum), dtype=torch.int32, device=dev)
+    sv_coef = torch.zeros(max(1, nrows_sum), dtype=torch.float64, device=dev)
+    rho = torch.zeros(max(1, nprob), dtype=torch.float64, device=dev)
+    nsv = torch.zeros(max(1, nprob), dtype=torch.int32, device=dev)
+    rows_cat = torch.cat(pool) if pool else torch.zeros(1, dtype=torch.int64, device=dev)
+    cat = lambda parts: np.concatenate(parts) if parts else np.zeros(1, dtype=np.int64)   # noqa: E731
+    qrows = rows_cat[to_dev(cat(qsrc))]
+    opos_d, qinfo_d, work_d = to_dev(cat(opos)), to_dev(qinfo), to_dev(work)
+    args = native.SvmDecArgs(
+        probs=native.ptr(Pd), nprob=nprob, y=native.ptr(y), C=native.ptr(C), alpha=native.ptr(alpha), G=native.ptr(G),
+        sv_idx=native.ptr(sv_idx), sv_coef=native.ptr(sv_coef), rho=native.ptr(rho), nsv=native.ptr(nsv),
+        Xrs=native.ptr(Xrs), X=native.ptr(data.X), d=data.d, work=native.ptr(work_d), nwork=work.shape[0],
+        qinfo=native.ptr(qinfo_d), qrows=native.ptr(qrows), opos=native.ptr(opos_d), out=native.ptr(out))
+    _native_call(data, "rho_sv", args)
+    _native_call(data, "decision", args)
+    launches = 2
+    dec = {k_: out[o:o + m] for k_, (o, m) in dec_off.items()}
+    cvdec = {k_: out[o:o + m] for k_, (o, m) in cv_off.items()}
+    preds: Dict[int, torch.Tensor] = {}
+    if not svr:
+        ms = [int(data.test_rows[t.split].numel()) for t in tasks]
+        poff = np.cumsum(ms) - np.asarray(ms)
+        pred = torch.zeros(max(1, int(sum(ms))), dtype=torch.int32, device=dev)
+        if len(pairs):
+            fit_tab = to_dev(np.stack([np.asarray(ms), poff], 1).astype(np.int64))
+            pair_off = to_dev(np.array([[dec_off.get((ti, pi), (-1, 0))[0] for pi in range(len(pairs))]
+                                        for ti in range(len(tasks))], dtype=np.int64))
+            args.fit_tab, args.pair_off, args.pred = native.ptr(fit_tab), native.ptr(pair_off), native.ptr(pred)
+            args.F, args.n_classes, args.max_m = len(tasks), data.n_classes, max(ms)
+            _native_call(data, "vote", args)
+            launches += 1
+        preds = {ti: pred[int(poff[ti]):int(poff[ti]) + ms[ti]] for ti in range(len(tasks))}
+    # ---- kept fits: rho, indices, coefficients and the support vectors' rows, once per batch --
+    models: Dict[int, list] = {}
+    host_reads = 0
+
+    def read(t) -> np.ndarray:   # every device-to-host copy of this phase goes through here
+        nonlocal host_reads
+        host_reads += 1
+        return t.cpu().numpy()
+
+    if keep_models:
+        rho_h, nsv_h, idx_h, cf_h = (read(a) for a in (rho, nsv, sv_idx, sv_coef))
+        outer = [k for k in range(nprob) if prob_of[k][3] < 0]
+        take = [pool_off[("rows", prob_of[k][2])] + idx_h[int(P[k]["roff"]):int(P[k]["roff"]) + int(nsv_h[k])]
+                for k in outer]
+        Xsv = read(data.X[rows_cat[to_dev(cat(take).astype(np.int64))]])
+        at = 0
+        for k in outer:
+            ti, pi, r0, n = prob_of[k][0], prob_of[k][1], int(P[k]["roff"]), int(nsv_h[k])
+            models.setdefault(ti, []).append({"sv": Xsv[at:at + n].copy(), "coef": cf_h[r0:r0 + n].copy(),
+                                              "rho": float(rho_h[k]), "pair": pairs[pi]})
+            at += n
+    fam.last_decision_stats = {"path": "batched", "problems": nprob, "queries": qtot, "launches": launches}
+    if os.environ.get("DML_SVM_DECISION_PAIRS"):   # benchmarks: the (query, support vector) pairs, one more read
+        fam.last_decision_stats["pairs"] = int((qinfo[:, 1] * read(nsv[:nprob]).astype(np.int64)).sum())
+    fam.last_decision_stats["host_reads"] = host_reads
+    return dec, cvdec, preds, models
 
 
 def _kernel_matrix(A: torch.Tensor, B: torch.Tensor, kernel: int, gamma: float, coef0: float, degree: int):

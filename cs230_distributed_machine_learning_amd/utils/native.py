@@ -158,6 +158,12 @@ EnetArgs = _i64_struct(
     ["Q", "q", "ynorm2", "gram_id", "l1", "l2", "positive", "max_iter", "tol", "w", "gap", "tol_eff", "n_iter",
      "F", "d", "G"],
 )
+# csrc/kernels/svm_args.h SvmDecArgs (post-solve phase of the SVM family: svm_decision.hip and its host twins)
+SvmDecArgs = _i64_struct(
+    "SvmDecArgs",
+    ["probs", "nprob", "y", "C", "alpha", "G", "sv_idx", "sv_coef", "rho", "nsv", "Xrs", "X", "d", "work", "nwork",
+     "qinfo", "qrows", "opos", "out", "fit_tab", "pair_off", "F", "n_classes", "max_m", "pred"],
+)
 ENET_D_TOO_LARGE = 3   # dml_enet_cd: d above dml_enet_max_d(), nothing was launched
 LrGradArgs = _i64_struct("LrGradArgs", ["rh", "rl", "unused", "xth", "xtl", "m_tiles", "n_tiles", "Kp", "S", "Kc", "out",
                                         "bk_off", "slab0", "mlive", "kskip"])
@@ -220,6 +226,12 @@ def cpu_lib() -> ctypes.CDLL:
             lib.dml_cpu_svm_platt_fit.argtypes = [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]
             lib.dml_cpu_svm_pair_proba.restype = c_i32
             lib.dml_cpu_svm_pair_proba.argtypes = [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]
+            lib.dml_cpu_svm_dec_sizeof_args.restype = c_i32
+            if lib.dml_cpu_svm_dec_sizeof_args() != ctypes.sizeof(SvmDecArgs):
+                raise RuntimeError("SvmDecArgs layout mismatch between C++ and Python")
+            for fn in (lib.dml_cpu_svm_rho_sv, lib.dml_cpu_svm_decision, lib.dml_cpu_svm_vote):
+                fn.restype = c_i32
+                fn.argtypes = [ctypes.POINTER(SvmDecArgs)]
             lib.dml_cpu_dp_sizeof_args.restype = c_i32
             lib.dml_cpu_dp_step.restype = c_i32
             lib.dml_cpu_dp_step.argtypes = [c_vp, c_i32]
@@ -313,6 +325,11 @@ def _register_optional(lib) -> None:
         "dml_svm_smo": (c_i32, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
         "dml_svm_platt_fit": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp]),
         "dml_svm_pair_proba": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
+        "dml_svm_dec_sizeof_args": (c_i32, []),
+        "dml_svm_dec_query_tile": (c_i32, []),
+        "dml_svm_rho_sv": (c_i32, [ctypes.POINTER(SvmDecArgs), c_vp]),
+        "dml_svm_decision": (c_i32, [ctypes.POINTER(SvmDecArgs), c_vp]),
+        "dml_svm_vote": (c_i32, [ctypes.POINTER(SvmDecArgs), c_vp]),
         "dml_split_moments": (c_i32, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_i32, c_vp, c_i64, c_vp]),
         "dml_lr_mfma_tile": (c_i32, []),
         "dml_lr_mfma_fwd": (c_i32, [ctypes.POINTER(LrFwdArgs), c_vp]),
@@ -387,6 +404,9 @@ def _register_optional(lib) -> None:
     if (getattr(lib, "dml_enet_sizeof_args", None) is not None
             and lib.dml_enet_sizeof_args() != ctypes.sizeof(EnetArgs)):
         raise RuntimeError("EnetArgs layout mismatch between HIP library and Python")
+    if (getattr(lib, "dml_svm_dec_sizeof_args", None) is not None
+            and lib.dml_svm_dec_sizeof_args() != ctypes.sizeof(SvmDecArgs)):
+        raise RuntimeError("SvmDecArgs layout mismatch between HIP library and Python")
     if getattr(lib, "dml_mae_sizeof_args", None) is not None and lib.dml_mae_sizeof_args() != ctypes.sizeof(MaeArgs):
         raise RuntimeError("MAE builder argument layout mismatch between HIP library and Python")
     if getattr(lib, "dml_lr_sizeof_fwd_args", None) is not None:
