@@ -22,6 +22,13 @@
 //                      partials, k_rank_ap_reduce adds a problem's blocks in block order.
 //   k_proba_stats      per fit: n, sum log p_y, the Brier sum, top-2 hits, bad; doubles in the same
 //                      fixed order (k_proba_reduce), counts as integer atomics.
+//   pair statistics    roc_auc_ovo*: per fit n[C] and U2[C][C], column c's keys of class c ranked against
+//                      those of every other class l.  k_pair_count (class counts: lane l of a wave
+//                      counts class l from ballots, one integer atomic per wave and class present),
+//                      k_pair_offsets (class offsets -> the F C C segment bounds), k_pair_scatter (a
+//                      C-way partition: an entry's C keys go to its class's slot in every column),
+//                      the segmented sort above, k_pair_reduce (a tile of sorted class-c keys against
+//                      the window of the class-l segment it can reach, staged in LDS when it fits).
 // ../runtime/rank_stats_cpu.cpp is the host twin (std::sort per segment; sums in this order).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -480,6 +487,214 @@ static int seg_sort_launch(SegSortArgs s, int64_t S, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 
+// ---- one-vs-one pair statistics (roc_auc_ovo*) ---------------------------------------------------
+// Per fit: n[l], the valid entries of class l, and U2[c][l] = sum over (i of class c, j of class l)
+// of 2 [s_c(i) > s_c(j)] + [s_c(i) == s_c(j)] on the keys of score column c.  Column c of fit f
+// owns [r0 C + c len, + len) of the key buffer, split into C class segments by the exclusive class
+// offsets; entries that cannot be placed fill the range from the back with the largest key, so the
+// last class segment ends with them and no slot of the buffer is left unwritten.
+constexpr int kPairWin = 8192;   // keys of the class-l window k_pair_reduce stages in LDS (32 KiB)
+
+struct PairRankArgs {
+  int64_t rows;         // int32 [total]
+  int64_t fit_row_off;  // int64 [F + 1]
+  int64_t score;        // float [total][C]
+  int64_t ycls;         // int32 [n]
+  int64_t n;
+  int64_t C;
+  int64_t F;
+  int64_t max_rows;     // entries of the longest fit
+  int64_t cls;          // int8 [total]: an entry's class, -1 when it cannot be placed (k_pair_count writes it)
+  int64_t cur;          // uint64 [F][C + 1]: the scatter's cursors, one per class and one for the unplaced
+  int64_t seg_off;      // int64 [F C C + 1]: the bounds of segment (f, c, l)
+  int64_t keys;         // uint32 [total * C]
+  int64_t tmp;          // uint32 [total * C]
+  int64_t hist;         // dml_seg_sort_hist_bytes(F C C, max_rows)
+  int64_t out;          // 8-byte slots [F][C + C C]: n[C], U2[C][C]
+  int64_t bad;          // int64 [F]
+  int64_t f0;           // first fit / problem of this launch (the entry point sets it)
+};
+
+// The lanes of this round whose class is this lane's index: one ballot per distinct class of the
+// wave.  With `base` (lane l: the next free slot of class l) it also hands every lane its slot and
+// advances the bases.
+__device__ __forceinline__ uint32_t pr_classes(int32_t t, int lane, uint32_t* base, uint32_t* slot) {
+  uint32_t mine = 0;
+  uint64_t rem = rs_ballot(t >= 0);
+  while (rem) {
+    const int k = wave::bcast(t, (int)__builtin_ctzll(rem));
+    const uint64_t m = rs_ballot(t == k);
+    if (base) {
+      const uint32_t b = wave::bcast(*base, k);
+      if (t == k) *slot = b + rs_below(m);
+    }
+    if (lane == k) mine = (uint32_t)__popcll(m);
+    rem &= ~m;
+  }
+  if (base) *base += mine;
+  return mine;
+}
+
+__global__ __launch_bounds__(256) void k_pair_count(PairRankArgs a) {
+  const int64_t f = a.f0 + blockIdx.y;
+  const int64_t* roff = RS_PTR(const int64_t, a.fit_row_off);
+  const int64_t r0 = roff[f], r1 = roff[f + 1];
+  const int64_t t0 = r0 + (int64_t)blockIdx.x * kRsTile;
+  if (t0 >= r1) return;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t w0 = t0 + (int64_t)w * kRsWaveKeys + lane;
+  const int C = (int)a.C;
+  const float* score = RS_PTR(const float, a.score);
+  int8_t* cls = RS_PTR(int8_t, a.cls);
+  uint32_t cnt = 0, nbad = 0;   // cnt: lane l counts the wave's entries of class l
+  for (int r = 0; r < kRsRounds; ++r) {
+    const int64_t i = w0 + r * 64;
+    int32_t t = -2;   // past the fit's end
+    if (i < r1) {
+      const int32_t row = RS_PTR(const int32_t, a.rows)[i];
+      t = -1;
+      if ((uint64_t)(int64_t)row < (uint64_t)a.n) {
+        const int32_t y = RS_PTR(const int32_t, a.ycls)[row];
+        if ((uint32_t)y < (uint32_t)C) t = y;
+      }
+      if (t >= 0) {
+        const float* s = score + i * C;
+        bool nan = false;
+        for (int k = 0; k < C; ++k) nan = nan || s[k] != s[k];
+        if (nan) t = -1;
+      }
+      nbad += t == -1 ? 1u : 0u;
+      cls[i] = (int8_t)t;
+    }
+    cnt += pr_classes(t, lane, nullptr, nullptr);
+  }
+  if (cnt) atomicAdd(RS_PTR(unsigned long long, a.out) + f * (C + C * C) + lane, (unsigned long long)cnt);
+  nbad = wave::sum(nbad, lane);
+  if (lane == 0 && nbad) atomicAdd(RS_PTR(unsigned long long, a.bad) + f, (unsigned long long)nbad);
+}
+
+// one thread per (fit, column): the bounds of its C class segments
+__global__ __launch_bounds__(256) void k_pair_offsets(PairRankArgs a) {
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t C = a.C;
+  if (q >= a.F * C) return;
+  const int64_t f = q / C, c = q - f * C;
+  const int64_t* roff = RS_PTR(const int64_t, a.fit_row_off);
+  const int64_t r0 = roff[f], len = roff[f + 1] - r0;
+  const int64_t* nf = RS_PTR(const int64_t, a.out) + f * (C + C * C);
+  int64_t* so = RS_PTR(int64_t, a.seg_off) + q * C;
+  int64_t run = r0 * C + c * len;
+  for (int64_t l = 0; l < C; ++l) {
+    so[l] = run;
+    run += nf[l];
+  }
+  if (q == a.F * C - 1) so[C] = roff[a.F] * C;
+}
+
+__global__ __launch_bounds__(256) void k_pair_scatter(PairRankArgs a) {
+  const int64_t f = a.f0 + blockIdx.y;
+  const int64_t* roff = RS_PTR(const int64_t, a.fit_row_off);
+  const int64_t r0 = roff[f], r1 = roff[f + 1], len = r1 - r0;
+  const int64_t t0 = r0 + (int64_t)blockIdx.x * kRsTile;
+  if (t0 >= r1) return;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t w0 = t0 + (int64_t)w * kRsWaveKeys + lane;
+  const int C = (int)a.C;
+  const int8_t* cls = RS_PTR(const int8_t, a.cls);
+  // lane l: the exclusive offset of class l within a column's range
+  const uint32_t nl = lane < C ? (uint32_t)RS_PTR(const int64_t, a.out)[f * (C + C * C) + lane] : 0u;
+  uint32_t base = wave::incl_scan(nl) - nl;
+  uint32_t cnt = 0, nb = 0;
+  for (int r = 0; r < kRsRounds; ++r) {
+    const int64_t i = w0 + r * 64;
+    const int32_t t = i < r1 ? (int32_t)cls[i] : -2;
+    cnt += pr_classes(t, lane, nullptr, nullptr);
+    nb += (uint32_t)__popcll(rs_ballot(t == -1));
+  }
+  // one cursor advance per wave and class present, one for the wave's unplaced entries
+  unsigned long long* cur = RS_PTR(unsigned long long, a.cur) + f * (C + 1);
+  if (cnt) base += (uint32_t)atomicAdd(cur + lane, (unsigned long long)cnt);
+  unsigned long long bb = 0;
+  if (lane == 0 && nb) bb = atomicAdd(cur + C, (unsigned long long)nb);
+  uint32_t bbase = (uint32_t)wave::bcast(bb, 0);
+  const float* score = RS_PTR(const float, a.score);
+  uint32_t* kb = RS_PTR(uint32_t, a.keys) + r0 * C;
+  for (int r = 0; r < kRsRounds; ++r) {
+    const int64_t i = w0 + r * 64;
+    const int32_t t = i < r1 ? (int32_t)cls[i] : -2;
+    uint32_t slot = 0;
+    pr_classes(t, lane, &base, &slot);
+    const uint64_t mb = rs_ballot(t == -1);
+    if (t == -1) slot = (uint32_t)(len - 1) - (bbase + rs_below(mb));
+    bbase += (uint32_t)__popcll(mb);
+    if (t >= -1) {
+      const float* s = score + i * C;
+      for (int c = 0; c < C; ++c) kb[(int64_t)c * len + slot] = t >= 0 ? rs_key(s[c]) : 0xFFFFFFFFu;
+    }
+  }
+}
+
+// rs_bound on the LDS window
+__device__ __forceinline__ int pr_bound_lds(const uint32_t* k, int lo, int hi, uint32_t v, bool upper) {
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    const uint32_t x = k[mid];
+    if (upper ? x <= v : x < v) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// grid = (tiles of the sorted class-c keys, problems (f, c, l)).  The tile is sorted, so every bound
+// it asks for lies in the window [lower bound of its first key, upper bound of its last key) of the
+// class-l segment: the window is staged in LDS when it holds at most kPairWin keys and searched in
+// global memory otherwise.
+__global__ __launch_bounds__(256) void k_pair_reduce(PairRankArgs a) {
+  __shared__ uint32_t win[kPairWin];
+  __shared__ unsigned long long ured[4];
+  const int64_t p = a.f0 + blockIdx.y;
+  const int64_t C = a.C, CC = C * C;
+  const int64_t f = p / CC, cl = p - f * CC, c = cl / C, l = cl - c * C;
+  if (c == l) return;
+  unsigned long long* of = RS_PTR(unsigned long long, a.out) + f * (C + CC);
+  const int64_t na = (int64_t)of[c], nb = (int64_t)of[l];
+  const int64_t t0 = (int64_t)blockIdx.x * kRsTile;
+  if (t0 >= na || nb == 0) return;   // block-uniform: before any barrier
+  const int64_t t1 = t0 + kRsTile < na ? t0 + kRsTile : na;
+  const int64_t* so = RS_PTR(const int64_t, a.seg_off) + (f * C + c) * C;
+  const uint32_t* A = RS_PTR(const uint32_t, a.keys) + so[c];
+  const uint32_t* B = RS_PTR(const uint32_t, a.keys) + so[l];
+  const int64_t lo = rs_bound(B, 0, nb, A[t0], false);
+  const int64_t hi = rs_bound(B, lo, nb, A[t1 - 1], true);
+  const int64_t wlen = hi - lo;
+  const bool staged = wlen <= kPairWin;
+  if (staged) {
+    for (int j = threadIdx.x; j < (int)wlen; j += 256) win[j] = B[lo + j];
+    __syncthreads();
+  }
+  unsigned long long u2 = 0;
+  for (int64_t i = t0 + threadIdx.x; i < t1; i += 256) {
+    const uint32_t v = A[i];
+    int64_t lt, le;
+    if (staged) {
+      lt = pr_bound_lds(win, 0, (int)wlen, v, false);
+      le = pr_bound_lds(win, (int)lt, (int)wlen, v, true);
+    } else {
+      lt = rs_bound(B + lo, 0, wlen, v, false);
+      le = rs_bound(B + lo, lt, wlen, v, true);
+    }
+    u2 += (unsigned long long)(2 * lo + lt + le);   // 2 lower + (upper - lower)
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  u2 = wave::sum(u2, lane);
+  if (lane == 0) ured[w] = u2;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const unsigned long long s = ured[0] + ured[1] + ured[2] + ured[3];
+    if (s) atomicAdd(of + C + c * C + l, s);
+  }
+}
+
 }  // namespace dml
 
 using namespace dml;
@@ -576,6 +791,47 @@ int dml_proba_stats(RankStatsArgs* a, hipStream_t st) {
   }
   b.f0 = 0;
   k_proba_reduce<<<(unsigned)((a->F * 2 + 255) / 256), 256, 0, st>>>(b, gx);
+  return hipGetLastError() == hipSuccess ? 0 : 1;
+}
+
+int dml_pair_rank_sizeof_args() { return (int)sizeof(PairRankArgs); }
+int dml_pair_rank_window() { return kPairWin; }
+
+// 0: launched; 1: a HIP error; 2: bad arguments.  Zeroes `out`, `bad` and `cur` itself.
+int dml_pair_rank_stats(PairRankArgs* a, hipStream_t st) {
+  if (a->F <= 0) return 0;
+  if (!a->fit_row_off || !a->out || !a->bad || !a->cur || !a->seg_off || a->C < 2 || a->C > kRsMaxC ||
+      a->max_rows < 0 || a->n < 0 || a->n > 2147483647LL || a->max_rows > 2147483647LL)
+    return 2;
+  const int64_t gx = (a->max_rows + kRsTile - 1) / kRsTile;
+  const int64_t C = a->C, P = a->F * C * C;
+  if (gx > 0 && (!a->rows || !a->score || !a->ycls || !a->cls || !a->keys || !a->tmp || !a->hist)) return 2;
+  if (hipMemsetAsync((void*)(uintptr_t)a->out, 0, (size_t)(a->F * (C + C * C)) * 8, st) != hipSuccess ||
+      hipMemsetAsync((void*)(uintptr_t)a->bad, 0, (size_t)a->F * 8, st) != hipSuccess ||
+      hipMemsetAsync((void*)(uintptr_t)a->cur, 0, (size_t)(a->F * (C + 1)) * 8, st) != hipSuccess)
+    return 1;
+  if (gx == 0) return 0;
+  PairRankArgs b = *a;
+  for (int64_t f0 = 0; f0 < a->F; f0 += kMaxGridY) {
+    b.f0 = f0;
+    k_pair_count<<<dim3((unsigned)gx, (unsigned)(a->F - f0 < kMaxGridY ? a->F - f0 : kMaxGridY)), 256, 0, st>>>(b);
+  }
+  k_pair_offsets<<<(unsigned)((a->F * C + 255) / 256), 256, 0, st>>>(b);
+  for (int64_t f0 = 0; f0 < a->F; f0 += kMaxGridY) {
+    b.f0 = f0;
+    k_pair_scatter<<<dim3((unsigned)gx, (unsigned)(a->F - f0 < kMaxGridY ? a->F - f0 : kMaxGridY)), 256, 0, st>>>(b);
+  }
+  SegSortArgs s = {};
+  s.src = a->keys;
+  s.dst = a->tmp;
+  s.seg_off = a->seg_off;
+  s.hist = a->hist;
+  s.gx = gx;
+  if (seg_sort_launch(s, P, st) != 0) return 1;
+  for (int64_t p0 = 0; p0 < P; p0 += kMaxGridY) {
+    b.f0 = p0;
+    k_pair_reduce<<<dim3((unsigned)gx, (unsigned)(P - p0 < kMaxGridY ? P - p0 : kMaxGridY)), 256, 0, st>>>(b);
+  }
   return hipGetLastError() == hipSuccess ? 0 : 1;
 }
 

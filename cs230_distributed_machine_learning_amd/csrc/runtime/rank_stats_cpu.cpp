@@ -1,5 +1,6 @@
 // rank_stats_cpu.cpp -- the statistics of the ranking and probability scorers on the host: the
-// twin of ../kernels/rank_stats.hip (dml_rank_stats, dml_proba_stats, dml_seg_sort_u32).  Same
+// twin of ../kernels/rank_stats.hip (dml_rank_stats, dml_proba_stats, dml_seg_sort_u32,
+// dml_pair_rank_stats).  Same
 // arguments, one per field, same outputs.  The kernel's radix sort is replaced by std::sort per
 // segment: sorted keys are unique, so the two agree bit for bit.  Every floating-point sum is
 // added in the kernel's order: a lane adds its entries of the tile in order, the 64 lanes of a
@@ -135,6 +136,63 @@ int dml_cpu_rank_stats(const int32_t* rows, const int64_t* fit_row_off, const fl
       put_double(o + 3, ap);
     }
     bad[f] = nbad;
+  }
+  return 0;
+}
+
+// The twin of dml_pair_rank_stats (roc_auc_ovo*).  out: 8-byte slots [F][C + C C] = n[C], the valid
+// entries of every class, then U2[C][C]: U2[c][l] = sum over (i of class c, j of class l) of
+// 2 [s_c(i) > s_c(j)] + [s_c(i) == s_c(j)] on the keys of score column c (diagonal 0); bad: int64 [F].
+int dml_cpu_pair_rank_stats(const int32_t* rows, const int64_t* fit_row_off, const float* score, const int32_t* ycls,
+                            int64_t n, int64_t C, int64_t F, int64_t max_rows, int64_t* out, int64_t* bad) {
+  if (F <= 0) return 0;
+  if (!fit_row_off || !out || !bad || C < 2 || C > kMaxC || max_rows < 0 || n < 0 || n > 2147483647LL ||
+      max_rows > 2147483647LL)
+    return 2;
+  if (max_rows > 0 && (!rows || !score || !ycls)) return 2;
+  const int64_t gx = (max_rows + kTile - 1) / kTile, slots = C + C * C;
+  memset(out, 0, (size_t)(F * slots) * 8);
+  memset(bad, 0, (size_t)F * 8);
+#pragma omp parallel for schedule(dynamic, 1)
+  for (int64_t f = 0; f < F; ++f) {
+    const int64_t r0 = fit_row_off[f];
+    int64_t r1 = fit_row_off[f + 1];
+    if (r1 > r0 + gx * kTile) r1 = r0 + gx * kTile;   // the launch's reach
+    int64_t* o = out + f * slots;
+    std::vector<std::vector<int64_t>> members((size_t)C);   // the valid entries of every class
+    for (int64_t i = r0; i < r1; ++i) {
+      const int32_t row = rows[i];
+      int32_t t = -1;
+      if ((uint64_t)(int64_t)row < (uint64_t)n) {
+        const int32_t y = ycls[row];
+        if ((uint32_t)y < (uint32_t)C) t = y;
+      }
+      for (int64_t k = 0; t >= 0 && k < C; ++k)
+        if (score[i * C + k] != score[i * C + k]) t = -1;
+      if (t < 0) bad[f] += 1;
+      else members[(size_t)t].push_back(i);
+    }
+    for (int64_t l = 0; l < C; ++l) o[l] = (int64_t)members[(size_t)l].size();
+    std::vector<std::vector<uint32_t>> seg((size_t)C);
+    for (int64_t c = 0; c < C; ++c) {
+      for (int64_t l = 0; l < C; ++l) {
+        seg[(size_t)l].clear();
+        for (int64_t i : members[(size_t)l]) seg[(size_t)l].push_back(rs_key(score[i * C + c]));
+        std::sort(seg[(size_t)l].begin(), seg[(size_t)l].end());
+      }
+      const std::vector<uint32_t>& A = seg[(size_t)c];
+      for (int64_t l = 0; l < C; ++l) {
+        if (l == c) continue;
+        const std::vector<uint32_t>& B = seg[(size_t)l];
+        uint64_t u2 = 0;
+        for (uint32_t v : A) {
+          const int64_t lt = std::lower_bound(B.begin(), B.end(), v) - B.begin();
+          const int64_t le = std::upper_bound(B.begin() + lt, B.end(), v) - B.begin();
+          u2 += (uint64_t)(2 * lt + (le - lt));
+        }
+        o[C + c * C + l] = (int64_t)u2;
+      }
+    }
   }
   return 0;
 }

@@ -113,8 +113,8 @@ def _batched_scores(data, tasks, outputs: Dict[int, FitOutput], scorer: str) -> 
     grouped by split (same held-out rows), their predictions stacked and scored together --
     instead of one reduction and one host sync per fit (a 2,560-fit LogisticRegression batch
     spent 0.27 s per search in per-fit syncs).  Exact: a mean of 0/1 counts is the same
-    double whatever the reduction order.  roc_auc, roc_auc_ovr and roc_auc_ovr_weighted are
-    batched too (``_rank_proba_scores``): their statistics are integers.  Every other scorer is
+    double whatever the reduction order.  roc_auc, roc_auc_ovr*, and roc_auc_ovo* are batched
+    too (``_rank_proba_scores``): their statistics are integers.  Every other scorer is
     a floating-point sum whose last place would move, and stays per fit."""
     if scorer in _EXACT_RANK and getattr(data, "is_gpu", False):
         # roc_auc*: one division of exact integer rank statistics, done as torch does it for device
@@ -142,20 +142,22 @@ def _batched_scores(data, tasks, outputs: Dict[int, FitOutput], scorer: str) -> 
     return dict(zip(ids, torch.cat(vals).cpu().tolist()))
 
 
-_EXACT_RANK = ("roc_auc", "roc_auc_ovr", "roc_auc_ovr_weighted")
+_EXACT_RANK = ("roc_auc", "roc_auc_ovr", "roc_auc_ovr_weighted", "roc_auc_ovo", "roc_auc_ovo_weighted")
 
 
 def _rank_proba_scores(data, tasks, outputs: Dict[int, FitOutput], names,
                        device_division: bool = False) -> Dict[int, Dict[str, float]]:
     """The ranking and probability scorers among ``names`` (``scoring.RANK_SCORERS``,
-    ``scoring.PROBA_SUM_SCORERS``) for every fit that hands over float32 scores on the targets'
-    device: {task_id: {scorer name: score}}.  The binary column (``proba[:, 1]``, or the decision
+    ``scoring.PROBA_SUM_SCORERS``, ``scoring.PAIR_SCORERS``) for every fit that hands over float32
+    scores on the targets' device: {task_id: {scorer name: score}}.  The binary column (``proba[:, 1]``, or the decision
     values when there are no probabilities) of those fits is concatenated once and
     ``scoring.rank_statistics`` runs once on it; the whole probability matrices are concatenated
-    once for one ``rank_statistics`` call (roc_auc_ovr*) and one ``proba_statistics`` call.  A fit
+    once for one ``rank_statistics`` call (roc_auc_ovr*), one ``pair_rank_statistics`` call
+    (roc_auc_ovo*, three classes or more) and one ``proba_statistics`` call.  A fit
     that is absent from the result -- float64 scores (SVC), another length or device, more classes
     than the kernels take, a row-sharded table -- is scored by ``scoring.score`` as before."""
-    names = [nm for nm in dict.fromkeys(names) if nm in scoring_mod.RANK_SCORERS or nm in scoring_mod.PROBA_SUM_SCORERS]
+    served = scoring_mod.RANK_SCORERS + scoring_mod.PROBA_SUM_SCORERS + scoring_mod.PAIR_SCORERS
+    names = [nm for nm in dict.fromkeys(names) if nm in served]
     C = int(getattr(data, "n_classes", 0) or 0)
     if not names or C < 2 or getattr(data, "is_row_shard", False):
         return {}
@@ -163,8 +165,9 @@ def _rank_proba_scores(data, tasks, outputs: Dict[int, FitOutput], names,
     col_names = [nm for nm in names if nm in ("roc_auc", "average_precision")] if C == 2 else []
     ovr_names = [nm for nm in names if nm.startswith("roc_auc_ovr")]
     sum_names = [nm for nm in names if nm in scoring_mod.PROBA_SUM_SCORERS]
+    pair_names = [nm for nm in names if nm in scoring_mod.PAIR_SCORERS] if C > 2 else []   # binary: per fit
     if C > scoring_mod.MAX_STAT_CLASSES:
-        ovr_names, sum_names = [], []
+        ovr_names, sum_names, pair_names = [], [], []
 
     def f32(v, shape):
         return isinstance(v, torch.Tensor) and v.dtype == torch.float32 and v.device == y_all.device and \
@@ -195,13 +198,18 @@ def _rank_proba_scores(data, tasks, outputs: Dict[int, FitOutput], names,
             for i, (t, _s) in enumerate(col):
                 res.setdefault(t.task_id, {}).update(
                     {nm: scoring_mod.score_from_rank_stats(nm, st[i], C, device_division) for nm in col_names})
-        if mat and (ovr_names or sum_names):
+        if mat and (ovr_names or sum_names or pair_names):
             rows, off, P = cat(mat)
             if ovr_names:
                 st = scoring_mod.rank_statistics(rows, off, P, y_all, C, pos0=0)
                 for i, (t, _s) in enumerate(mat):
                     res.setdefault(t.task_id, {}).update(
                         {nm: scoring_mod.score_from_rank_stats(nm, st[i], C, device_division) for nm in ovr_names})
+            if pair_names:
+                st = scoring_mod.pair_rank_statistics(rows, off, P, y_all, C)
+                for i, (t, _s) in enumerate(mat):
+                    res.setdefault(t.task_id, {}).update(
+                        {nm: scoring_mod.score_from_pair_stats(nm, st[i], C, device_division) for nm in pair_names})
             if sum_names:
                 ps = scoring_mod.proba_statistics(rows, off, P, y_all, C, want=scoring_mod.proba_want(sum_names))
                 for i, (t, _s) in enumerate(mat):
@@ -228,9 +236,9 @@ def _multi_scores(data, tasks, outputs: Dict[int, FitOutput], pairs, clf: bool) 
     {task_id: {label: score}}.  The predictions of the whole family batch are stacked and
     ``scoring.fit_statistics`` runs once (one launch, one device->host read); every metric in
     ``scoring.STAT_SCORERS`` is derived from that read-back, and the ranking and probability
-    scorers from the batched rank and probability statistics (``_rank_proba_scores``).  The median
-    scorers and roc_auc_ovo* go through ``scoring.score`` per fit, as in a single-metric job -- and so does a fit
-    whose predictions are not the kernel's types (float64 regression predictions are scored in
+    scorers from the batched rank and probability statistics (``_rank_proba_scores``, roc_auc_ovo*
+    included).  The median scorers go through ``scoring.score`` per fit, as in a single-metric
+    job -- and so does a fit whose predictions are not the kernel's types (float64 regression predictions are scored in
     float64, not rounded to float32), and every fit of a row-sharded table (its resident targets
     are one rank's)."""
     y_all = data.y_cls if clf else data.y_reg

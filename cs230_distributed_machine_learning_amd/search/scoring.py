@@ -772,6 +772,103 @@ def segmented_sort_u32(keys: torch.Tensor, seg_off) -> torch.Tensor:
     return out
 
 
+# ---- one-vs-one pair statistics (roc_auc_ovo, roc_auc_ovo_weighted; docs/RANK_SCORES.md) ----------
+PAIR_SCORERS = ("roc_auc_ovo", "roc_auc_ovo_weighted")
+
+
+def pair_dtype(n_classes: int) -> np.dtype:
+    C = int(n_classes)
+    return np.dtype([("n", "<i8", (C,)), ("u2", "<u8", (C, C))])
+
+
+def pair_rank_statistics(rows: torch.Tensor, fit_row_off, proba: torch.Tensor, y: torch.Tensor,
+                         n_classes: int) -> np.ndarray:
+    """One-vs-one rank statistics of F fits, inputs as ``proba_statistics``.  Returns a
+    ``pair_dtype(C)`` record array [F]: ``n[l]``, the fit's entries of class l, and ``u2[c, l]`` =
+    sum over (i of class c, j of class l) of 2 [p_c(i) > p_c(j)] + [p_c(i) == p_c(j)] (diagonal 0),
+    so the AUC of class c against class l on column c is ``u2[c, l] * 0.5 / (n[c] * n[l])``.  An
+    entry with a NaN in any column, a target outside [0, C) or a row id outside ``y`` raises and
+    names the fit.
+
+    ``dml_pair_rank_stats`` of csrc/kernels/rank_stats.hip on the device of ``proba`` (a C-way
+    partition, the segmented radix sort over the F C C class segments, the pair reduce), its host
+    twin for CPU tensors; one device->host read per call."""
+    from ..utils import native
+
+    C = int(n_classes)
+    if proba.dim() != 2 or int(proba.shape[1]) != C or C > MAX_STAT_CLASSES:
+        raise ValueError(f"pair_rank_statistics: proba must be [total, n_classes] with at most {MAX_STAT_CLASSES} "
+                         f"classes")
+    off, F, rows, proba, y = _stat_inputs("pair_rank_statistics", rows, fit_row_off, proba, y, C, C)
+    n, slots = int(y.numel()), C + C * C
+    if F == 0:
+        return np.zeros(0, dtype=pair_dtype(C))
+    dev = proba.device
+    if dev.type == "cuda":
+        lib = native.hip_lib()
+        if getattr(lib, "dml_pair_rank_stats", None) is None:
+            raise RuntimeError("the HIP library has no dml_pair_rank_stats: rebuild it")
+        raw = torch.empty(F * slots + F, dtype=torch.int64, device=dev)   # the statistics, then bad [F]
+        chunks = list(_fit_chunks(off, C, RANK_CHUNK_KEYS))
+        n_ent = max(int(off[c1] - off[c0]) for c0, c1 in chunks)
+        n_fit = max(c1 - c0 for c0, c1 in chunks)
+        hist_b = max(int(lib.dml_seg_sort_hist_bytes(n_fit * C * C, int(np.diff(off).max()))), 4)
+        keys = torch.empty(max(1, n_ent * C), dtype=torch.int32, device=dev)
+        tmp = torch.empty(max(1, n_ent * C), dtype=torch.int32, device=dev)
+        hist = torch.empty(hist_b // 4, dtype=torch.int32, device=dev)
+        cls = torch.empty(max(1, n_ent), dtype=torch.int8, device=dev)
+        cur = torch.empty(n_fit * (C + 1), dtype=torch.int64, device=dev)
+        seg_off = torch.empty(n_fit * C * C + 1, dtype=torch.int64, device=dev)
+        with torch.cuda.device(dev):
+            for c0, c1 in chunks:
+                off_d = torch.from_numpy(off[c0:c1 + 1] - off[c0]).to(dev)
+                e0 = int(off[c0])
+                a = native.PairRankArgs(
+                    rows=native.ptr(rows) + 4 * e0, fit_row_off=native.ptr(off_d), score=native.ptr(proba) + 4 * e0 * C,
+                    ycls=native.ptr(y), n=n, C=C, F=c1 - c0, max_rows=int(np.diff(off[c0:c1 + 1]).max()),
+                    cls=native.ptr(cls), cur=native.ptr(cur), seg_off=native.ptr(seg_off), keys=native.ptr(keys),
+                    tmp=native.ptr(tmp), hist=native.ptr(hist), out=native.ptr(raw) + 8 * c0 * slots,
+                    bad=native.ptr(raw) + 8 * (F * slots + c0), f0=0)
+                rc = lib.dml_pair_rank_stats(a, native.stream_handle(dev))
+                if rc != 0:
+                    raise RuntimeError(f"dml_pair_rank_stats failed (status {rc})")
+        st = raw.cpu().numpy()   # the call's one device->host read
+    else:
+        lib = native.cpu_lib()
+        st = np.zeros(F * slots + F, dtype=np.int64)
+        rc = lib.dml_cpu_pair_rank_stats(native.ptr(rows), native.ptr(off), native.ptr(proba), native.ptr(y), n, C, F,
+                                         int(np.diff(off).max()), native.ptr(st), native.ptr(st) + 8 * F * slots)
+        if rc != 0:
+            raise RuntimeError(f"dml_cpu_pair_rank_stats failed (status {rc})")
+    _raise_bad("pair_rank_statistics", st[F * slots:])
+    return np.ascontiguousarray(st[:F * slots]).view(pair_dtype(C)).reshape(F)
+
+
+def score_from_pair_stats(name: str, rec, n_classes: int, device_division: bool = False) -> float:
+    """``score(name, ...)`` (``PAIR_SCORERS``) of one fit from its ``pair_rank_statistics`` record:
+    the expressions of ``_multiclass_auc`` on exact integers, pair (a, b) being the mean of the AUC
+    of a against b on column a and of b against a on column b, weighted by ``n[a] + n[b]`` for
+    ``_weighted``.  A class without entries makes its pairs, and so the score, NaN.
+    ``device_division``: as ``score_from_rank_stats``."""
+    if name not in PAIR_SCORERS:
+        raise ValueError(f"scorer {name!r} is not computable from pair statistics")
+    C = int(n_classes)
+    n = np.asarray(rec["n"], dtype=np.int64).reshape(C).astype(np.float64)
+    if n.sum() == 0:
+        return float("nan")
+    half = np.asarray(rec["u2"], dtype=np.uint64).reshape(C, C).astype(np.float64) * 0.5
+    with np.errstate(divide="ignore", invalid="ignore"):
+        den = n[:, None] * n[None, :]
+        auc = half * (1.0 / den) if device_division else half / den
+        auc[den == 0] = np.nan
+    ia, ib = np.triu_indices(C, 1)   # a < b, row-major: the order of _multiclass_auc's loops
+    v = torch.from_numpy((auc[ia, ib] + auc[ib, ia]) / 2.0)
+    if name.endswith("_weighted"):
+        w = torch.from_numpy(n[ia] + n[ib])
+        return float((v * w).sum() / w.sum())
+    return float(v.mean())
+
+
 def _auc_from_rank(rec, device_division: bool = False) -> float:
     n_pos, n_neg = int(rec["n_pos"]), int(rec["n_neg"])
     if n_pos == 0 or n_neg == 0:

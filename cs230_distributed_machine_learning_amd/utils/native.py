@@ -145,6 +145,12 @@ RankStatsArgs = _i64_struct(
     ["rows", "fit_row_off", "score", "ycls", "n", "C", "K", "pos0", "F", "max_rows", "want", "keys", "tmp", "hist",
      "part", "out", "bad", "phase", "f0"],
 )
+# csrc/kernels/rank_stats.hip PairRankArgs (per-fit class counts and one-vs-one pair rank counts)
+PairRankArgs = _i64_struct(
+    "PairRankArgs",
+    ["rows", "fit_row_off", "score", "ycls", "n", "C", "F", "max_rows", "cls", "cur", "seg_off", "keys", "tmp", "hist",
+     "out", "bad", "f0"],
+)
 # csrc/kernels/forest_mae.hip (criterion="absolute_error" builder)
 MaeArgs = _i64_struct(
     "MaeArgs",
@@ -220,6 +226,8 @@ def cpu_lib() -> ctypes.CDLL:
             lib.dml_cpu_rank_stats.argtypes = [c_vp] * 4 + [c_i64] * 7 + [c_vp, c_vp]
             lib.dml_cpu_proba_stats.restype = c_i32
             lib.dml_cpu_proba_stats.argtypes = [c_vp] * 4 + [c_i64] * 5 + [c_vp]
+            lib.dml_cpu_pair_rank_stats.restype = c_i32
+            lib.dml_cpu_pair_rank_stats.argtypes = [c_vp] * 4 + [c_i64] * 4 + [c_vp, c_vp]
             lib.dml_cpu_svm_sizeof_prob.restype = c_i32
             lib.dml_cpu_svm_smo.argtypes = [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]
             lib.dml_cpu_svm_platt_fit.restype = c_i32
@@ -365,6 +373,9 @@ def _register_optional(lib) -> None:
         "dml_seg_sort_u32": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp]),
         "dml_rank_stats": (c_i32, [ctypes.POINTER(RankStatsArgs), c_vp]),
         "dml_proba_stats": (c_i32, [ctypes.POINTER(RankStatsArgs), c_vp]),
+        "dml_pair_rank_sizeof_args": (c_i32, []),
+        "dml_pair_rank_window": (c_i32, []),
+        "dml_pair_rank_stats": (c_i32, [ctypes.POINTER(PairRankArgs), c_vp]),
         "dml_exp_hist": (c_i32, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
         "dml_forest_release_scratch": (c_i32, []),
         "dml_forest_block_stash_planes": (c_i32, []),
@@ -401,6 +412,9 @@ def _register_optional(lib) -> None:
     if (getattr(lib, "dml_rank_stats_sizeof_args", None) is not None
             and lib.dml_rank_stats_sizeof_args() != ctypes.sizeof(RankStatsArgs)):
         raise RuntimeError("RankStatsArgs layout mismatch between HIP library and Python")
+    if (getattr(lib, "dml_pair_rank_sizeof_args", None) is not None
+            and lib.dml_pair_rank_sizeof_args() != ctypes.sizeof(PairRankArgs)):
+        raise RuntimeError("PairRankArgs layout mismatch between HIP library and Python")
     if (getattr(lib, "dml_enet_sizeof_args", None) is not None
             and lib.dml_enet_sizeof_args() != ctypes.sizeof(EnetArgs)):
         raise RuntimeError("EnetArgs layout mismatch between HIP library and Python")
