@@ -90,6 +90,13 @@ template <int MODE> constexpr int block_nt() { return MODE == 1 ? DML_BLOCK_NT :
 // then the ballots); 0: the per-position stash / gather branch (A/B builds; docs/PARTITION_LOADS.md)
 #define DML_PART_STRAIGHT 1
 #endif
+#ifndef DML_HIST_SHORT
+// block tier, first feature group on row windows (runw).  1: the chunk pipeline loads no phantom
+// chunk: a chunk past the node's last issues no row-line loads and is not waited for (the loop
+// used to issue two whole windows of row 0's line behind a node's last chunk and wait for each).
+// 0: the loop as it was (A/B builds; docs/HIST_SHORT.md)
+#define DML_HIST_SHORT 1
+#endif
 #ifndef DML_NODES_WPE_WAVE
 #define DML_NODES_WPE_WAVE 4   // wave tier (binary): 2 / 3 / 5 / 6 measured slower (ROUND3.md)
 #endif
@@ -159,13 +166,18 @@ template <int MODE> constexpr int block_nt() { return MODE == 1 ? DML_BLOCK_NT :
 
 // optional per-phase cycle accounting of the fused node kernel (-DDML_PHASE_PROF builds only)
 #ifdef DML_PHASE_PROF
+#ifndef DML_PHASE_CHUNKS
+#define DML_PHASE_CHUNKS 4     // [3][3] sums the cycles of block-tier nodes of at most this many chunks of NT rows
+#endif
 // [0] wave tier, [1] block tier, [2] subtree tier phases (slot 7: nodes), [3] rows per tier +
 // subtree internal-node counts by evaluation path
 __device__ unsigned long long g_phase[4][8];
 #define PH_BEGIN uint64_t _pt = clock64(); uint64_t _acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #define PH(i) if (threadIdx.x == 0) { const uint64_t _n = clock64(); _acc[i] += _n - _pt; _pt = _n; }
 #define PH_END(t) if (threadIdx.x == 0) { _acc[7] = 1; for (int _i = 0; _i < 8; ++_i) atomicAdd(&g_phase[t][_i], _acc[_i]); \
-                                            atomicAdd(&g_phase[3][t], (unsigned long long)on.count); }
+                                            atomicAdd(&g_phase[3][t], (unsigned long long)on.count); \
+                                            if ((t) == 1 && on.count <= DML_PHASE_CHUNKS * (int)blockDim.x) { /* [3][3]: cycles of block-tier nodes of <= DML_PHASE_CHUNKS chunks */ \
+                                              uint64_t _s = 0; for (int _i = 0; _i < 7; ++_i) _s += _acc[_i]; atomicAdd(&g_phase[3][3], _s); } }
 #define PH_CNT(i, v) if (threadIdx.x == 0) atomicAdd(&g_phase[3][i], (unsigned long long)(v));
 #define PH_ARGS_DECL , uint64_t& _pt, uint64_t* _acc
 #define PH_ARGS_PASS , _pt, _acc
@@ -1699,6 +1711,10 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
             const uint4 q = xr[k];
             w[4 * k] = q.x; w[4 * k + 1] = q.y; w[4 * k + 2] = q.z; w[4 * k + 3] = q.w;
           }
+#ifdef DML_X2_WINDOW   // sensitivity build: every window load's line looked up twice (the second a dword of it)
+#pragma unroll
+          for (int k = 0; k < 7; ++k) w[4 * k] |= ((const uint32_t*)xr)[4 * k + ((uint32_t)c.n >> 31)];
+#endif
         };
         // the group's bins stay packed 4 x u8 per register between extract and consume (the
         // layout of the row's bscr slot): 2 x ceil(G/4) registers for the two chunks in flight
@@ -1736,6 +1752,26 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
         PRaw pA = payload_fetch<MODE, PK>(c, ty, rA), pB;
         extract(win, bA);
         bool vA = rA != INV, vB = false;
+#if DML_HIST_SHORT
+        // no phantom chunks: a chunk past the node's last loads no row lines and is not waited
+        // for (wave-uniform scalar branches around whole window loads); its row ids are INV in
+        // every lane, so its consume adds nothing and its never-extracted bins are never read
+        for (int base = 0; base < cnt; base += 2 * NT) {
+          const bool moreB = base + NT < cnt, moreA = base + 2 * NT < cnt;
+          if (moreB) load_win(rB, win);
+          pB = payload_fetch<MODE, PK>(c, ty, rB);
+          rA = row_at(base + 2 * NT + tid);
+          consume(base, vA, bA, pA);
+          if (moreB) extract(win, bB);
+          vB = rB != INV;
+          if (moreA) load_win(rA, win);
+          pA = payload_fetch<MODE, PK>(c, ty, rA);
+          rB = row_at(base + 3 * NT + tid);
+          consume(base + NT, vB, bB, pB);
+          if (moreA) extract(win, bA);
+          vA = rA != INV;
+        }
+#else
         for (int base = 0; base < cnt; base += 2 * NT) {
           load_win(rB, win);                      // chunk k+1's row lines
           pB = payload_fetch<MODE, PK>(c, ty, rB);
@@ -1750,6 +1786,7 @@ __global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? 
           extract(win, bA);
           vA = rA != INV;
         }
+#endif
       };
       if (DML_ROW_WINDOWS && NT > 64 && pos == 0 && g >= 8 && d <= 112 && (c.ld & 15) == 0 && c.ld >= 112 &&
           (((uintptr_t)c.Xb) & 15) == 0) {

@@ -15,6 +15,7 @@ for t, tn in enumerate(["wave(64)", "block"]):
     tot = v[:7].sum()
     rows = float(out[24 + t])
     print(tn, f"nodes={int(v[7])} rows/node={rows/n:.0f} cycles/node={tot/n:.0f}", "  ".join(f"{names[i]}={v[i]/n:.0f} ({100*v[i]/tot:.0f}%)" for i in range(7)))
+print(f"block nodes of <= DML_PHASE_CHUNKS (default 4) chunks: {100 * float(out[27]) / max(1.0, out[8:15].astype(float).sum()):.1f}% of the block tier's cycles")
 v = out[16:24].astype(float)
 n = v[7] or 1
 tot = v[:5].sum()
