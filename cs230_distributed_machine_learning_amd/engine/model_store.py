@@ -9,7 +9,8 @@ with ``allow_pickle=False``, so downloading and loading a model executes nothing
 Kinds: ``forest`` (pool layout of ops/forest_ops.py + bin edges),
 ``linear_logistic``, ``linear_regression``, ``knn`` (training rows), ``gbrt`` (stage trees),
 ``svm`` (support vectors + dual coefficients per one-vs-one machine), ``pca`` (mean,
-components, explained variances, noise variance).
+components, explained variances, noise variance), ``qda`` (class means, rotations, regularised
+variances and priors).
 
 ``load_predictor(path)`` wraps an artefact in an estimator-like object (``predict``,
 ``predict_proba`` / ``decision_function`` for classifiers, ``score``, ``transform`` for
@@ -32,7 +33,7 @@ _ARRAY_KEYS = ("nodes", "vals", "edges", "coef", "intercept", "X", "y", "init", 
                "oob_decision_function", "oob_prediction", "permutation_importances", "permutation_importances_mean",
                "permutation_importances_std", "permutation_baseline_score", "permutation_rows", "pd_features",
                "pd_grid_off", "pd_grid_values", "pd_average", "pd_rows", "train_score", "oob_scores", "oob_improvement",
-               "staged_test_score", "staged_test_loss")
+               "staged_test_score", "staged_test_loss", "priors", "means", "rotations", "scalings", "n_kept")
 
 
 def save_model(model: Dict[str, Any], path: str) -> str:
@@ -131,6 +132,10 @@ def predict(model: Dict[str, Any], X: np.ndarray) -> np.ndarray:
         from ..models.transformers import pca_transform_numpy
 
         return pca_transform_numpy(model, X)   # a transformer's "prediction" is its projection
+    if kind == "qda":
+        from ..models.discriminant import qda_decision_numpy
+
+        return np.asarray(classes)[qda_decision_numpy(model, X).argmax(1)]
     raise ValueError(f"unknown model kind {kind!r}")
 
 
@@ -232,6 +237,11 @@ class Predictor:
                                float(self.model["coef0"]), int(self.model["degree"]))
             dv = (K @ torch.from_numpy(np.asarray(m["coef"], dtype=np.float64)).to(K.dtype) - m["rho"]).numpy()
             return -dv   # sklearn's binary sign: positive -> classes_[1]
+        if self.kind == "qda":
+            from ..models.discriminant import qda_decision_numpy
+
+            dec = qda_decision_numpy(self.model, X)
+            return dec[:, 1] - dec[:, 0] if dec.shape[1] == 2 else dec   # sklearn's binary form
         raise AttributeError(f"{self.model_type} artefact has no decision_function")
 
     def predict_proba(self, X) -> np.ndarray:
@@ -289,6 +299,10 @@ class Predictor:
 
             if svm_has_proba(self.model):   # fitted with probability=True: probA / probB per machine
                 return svm_proba_numpy(self.model, X)
+        if kind == "qda":
+            from ..models.discriminant import qda_decision_numpy
+
+            return _softmax(qda_decision_numpy(self.model, X))
         raise AttributeError(f"{self.model_type} has no predict_proba (sklearn's default probability=False)")
 
     # ---- fitted forest attributes (sklearn's names; AttributeError when the artefact lacks one) ----
@@ -332,6 +346,30 @@ class Predictor:
         if self.kind != "linear_regression":
             raise AttributeError(f"{self.model_type} artefact has no {name}")
         return self.model
+
+    # ---- fitted QuadraticDiscriminantAnalysis attributes (sklearn's names and shapes) --------------
+    def _qda(self, name: str):
+        if self.kind != "qda":
+            raise AttributeError(f"{self.model_type} artefact has no {name}")
+        return self.model
+
+    @property
+    def means_(self) -> np.ndarray:
+        return np.asarray(self._qda("means_")["means"], dtype=np.float64)
+
+    @property
+    def priors_(self) -> np.ndarray:
+        return np.asarray(self._qda("priors_")["priors"], dtype=np.float64)
+
+    @property
+    def rotations_(self) -> list:
+        m = self._qda("rotations_")
+        return [np.asarray(m["rotations"][c], dtype=np.float64)[:, :int(k)] for c, k in enumerate(m["n_kept"])]
+
+    @property
+    def scalings_(self) -> list:
+        m = self._qda("scalings_")
+        return [np.asarray(m["scalings"][c], dtype=np.float64)[:int(k)] for c, k in enumerate(m["n_kept"])]
 
     @property
     def coef_(self) -> np.ndarray:

@@ -106,7 +106,7 @@ def _ensure_loaded():
     if _loaded:
         return
     _loaded = True
-    from . import forest, linear, neighbors, boosting, svm, transformers  # noqa: F401
+    from . import forest, linear, neighbors, boosting, svm, transformers, discriminant  # noqa: F401
 
 
 # ---- common parameter helpers ---------------------------------------------------------

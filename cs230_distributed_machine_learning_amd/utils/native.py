@@ -170,6 +170,15 @@ SvmDecArgs = _i64_struct(
     ["probs", "nprob", "y", "C", "alpha", "G", "sv_idx", "sv_coef", "rho", "nsv", "Xrs", "X", "d", "work", "nwork",
      "qinfo", "qrows", "opos", "out", "fit_tab", "pair_off", "F", "n_classes", "max_m", "pred"],
 )
+# csrc/kernels/qda_args.h (QuadraticDiscriminantAnalysis: qda.hip and its host twin)
+QdaMomArgs = _i64_struct(
+    "QdaMomArgs", ["X", "ld", "n", "d", "shift", "perm", "cell_off", "n_cells", "parts", "part", "out"])
+QdaScoreArgs = _i64_struct(
+    "QdaScoreArgs",
+    ["X", "ld", "n", "d", "rows", "row_off", "S", "max_rows", "total_rows", "C", "NC", "mu", "V", "inv", "cst", "pred",
+     "dec"],
+)
+QDA_TOO_LARGE = 3      # dml_qda_*: d or the candidate count above the kernel's limit, nothing was launched
 ENET_D_TOO_LARGE = 3   # dml_enet_cd: d above dml_enet_max_d(), nothing was launched
 LrGradArgs = _i64_struct("LrGradArgs", ["rh", "rl", "unused", "xth", "xtl", "m_tiles", "n_tiles", "Kp", "S", "Kc", "out",
                                         "bk_off", "slab0", "mlive", "kskip"])
@@ -248,6 +257,15 @@ def cpu_lib() -> ctypes.CDLL:
                 raise RuntimeError("EnetArgs layout mismatch between C++ and Python")
             lib.dml_cpu_enet_cd.restype = c_i32
             lib.dml_cpu_enet_cd.argtypes = [ctypes.POINTER(EnetArgs)]
+            lib.dml_cpu_qda_sizeof_mom_args.restype = c_i32
+            lib.dml_cpu_qda_sizeof_score_args.restype = c_i32
+            if (lib.dml_cpu_qda_sizeof_mom_args() != ctypes.sizeof(QdaMomArgs)
+                    or lib.dml_cpu_qda_sizeof_score_args() != ctypes.sizeof(QdaScoreArgs)):
+                raise RuntimeError("QDA argument layout mismatch between C++ and Python")
+            lib.dml_cpu_qda_class_moments.restype = c_i32
+            lib.dml_cpu_qda_class_moments.argtypes = [ctypes.POINTER(QdaMomArgs)]
+            lib.dml_cpu_qda_score.restype = c_i32
+            lib.dml_cpu_qda_score.argtypes = [ctypes.POINTER(QdaScoreArgs)]
             _cpu = lib
         return _cpu
 
@@ -393,6 +411,12 @@ def _register_optional(lib) -> None:
         "dml_enet_problems_per_block": (c_i32, [c_i64]),
         "dml_enet_cd": (c_i32, [ctypes.POINTER(EnetArgs), c_vp]),
         "dml_enet_cd_plain": (c_i32, [ctypes.POINTER(EnetArgs), c_vp]),
+        "dml_qda_sizeof_mom_args": (c_i32, []),
+        "dml_qda_sizeof_score_args": (c_i32, []),
+        "dml_qda_max_d": (c_i32, []),
+        "dml_qda_max_candidates": (c_i32, []),
+        "dml_qda_class_moments": (c_i32, [ctypes.POINTER(QdaMomArgs), c_vp]),
+        "dml_qda_score": (c_i32, [ctypes.POINTER(QdaScoreArgs), c_vp]),
     }
     for name, (res, args) in table.items():
         fn = getattr(lib, name, None)
@@ -418,6 +442,10 @@ def _register_optional(lib) -> None:
     if (getattr(lib, "dml_enet_sizeof_args", None) is not None
             and lib.dml_enet_sizeof_args() != ctypes.sizeof(EnetArgs)):
         raise RuntimeError("EnetArgs layout mismatch between HIP library and Python")
+    if (getattr(lib, "dml_qda_sizeof_mom_args", None) is not None
+            and (lib.dml_qda_sizeof_mom_args() != ctypes.sizeof(QdaMomArgs)
+                 or lib.dml_qda_sizeof_score_args() != ctypes.sizeof(QdaScoreArgs))):
+        raise RuntimeError("QDA argument layout mismatch between HIP library and Python")
     if (getattr(lib, "dml_svm_dec_sizeof_args", None) is not None
             and lib.dml_svm_dec_sizeof_args() != ctypes.sizeof(SvmDecArgs)):
         raise RuntimeError("SvmDecArgs layout mismatch between HIP library and Python")
