@@ -10,7 +10,8 @@ Kinds: ``forest`` (pool layout of ops/forest_ops.py + bin edges),
 ``linear_logistic``, ``linear_regression``, ``knn`` (training rows), ``gbrt`` (stage trees),
 ``svm`` (support vectors + dual coefficients per one-vs-one machine), ``pca`` (mean,
 components, explained variances, noise variance), ``qda`` (class means, rotations, regularised
-variances and priors).
+variances and priors), ``lda`` (class means, priors, the C x d coefficients and intercepts, and
+the pooled covariance where sklearn keeps one).
 
 ``load_predictor(path)`` wraps an artefact in an estimator-like object (``predict``,
 ``predict_proba`` / ``decision_function`` for classifiers, ``score``, ``transform`` for
@@ -33,7 +34,8 @@ _ARRAY_KEYS = ("nodes", "vals", "edges", "coef", "intercept", "X", "y", "init", 
                "oob_decision_function", "oob_prediction", "permutation_importances", "permutation_importances_mean",
                "permutation_importances_std", "permutation_baseline_score", "permutation_rows", "pd_features",
                "pd_grid_off", "pd_grid_values", "pd_average", "pd_rows", "train_score", "oob_scores", "oob_improvement",
-               "staged_test_score", "staged_test_loss", "priors", "means", "rotations", "scalings", "n_kept")
+               "staged_test_score", "staged_test_loss", "priors", "means", "rotations", "scalings", "n_kept",
+               "covariance")
 
 
 def save_model(model: Dict[str, Any], path: str) -> str:
@@ -136,6 +138,10 @@ def predict(model: Dict[str, Any], X: np.ndarray) -> np.ndarray:
         from ..models.discriminant import qda_decision_numpy
 
         return np.asarray(classes)[qda_decision_numpy(model, X).argmax(1)]
+    if kind == "lda":
+        from ..models.discriminant import lda_decision_numpy
+
+        return np.asarray(classes)[lda_decision_numpy(model, X).argmax(1)]
     raise ValueError(f"unknown model kind {kind!r}")
 
 
@@ -242,6 +248,11 @@ class Predictor:
 
             dec = qda_decision_numpy(self.model, X)
             return dec[:, 1] - dec[:, 0] if dec.shape[1] == 2 else dec   # sklearn's binary form
+        if self.kind == "lda":
+            from ..models.discriminant import lda_decision_numpy
+
+            dec = lda_decision_numpy(self.model, X)
+            return dec[:, 1] - dec[:, 0] if dec.shape[1] == 2 else dec
         raise AttributeError(f"{self.model_type} artefact has no decision_function")
 
     def predict_proba(self, X) -> np.ndarray:
@@ -303,6 +314,10 @@ class Predictor:
             from ..models.discriminant import qda_decision_numpy
 
             return _softmax(qda_decision_numpy(self.model, X))
+        if kind == "lda":   # sklearn: softmax of the class scores (for two classes, the sigmoid of their difference)
+            from ..models.discriminant import lda_decision_numpy
+
+            return _softmax(lda_decision_numpy(self.model, X))
         raise AttributeError(f"{self.model_type} has no predict_proba (sklearn's default probability=False)")
 
     # ---- fitted forest attributes (sklearn's names; AttributeError when the artefact lacks one) ----
@@ -347,19 +362,19 @@ class Predictor:
             raise AttributeError(f"{self.model_type} artefact has no {name}")
         return self.model
 
-    # ---- fitted QuadraticDiscriminantAnalysis attributes (sklearn's names and shapes) --------------
-    def _qda(self, name: str):
-        if self.kind != "qda":
+    # ---- fitted discriminant-analysis attributes (sklearn's names and shapes) ----------------------
+    def _qda(self, name: str, kinds=("qda",)):
+        if self.kind not in kinds:
             raise AttributeError(f"{self.model_type} artefact has no {name}")
         return self.model
 
     @property
     def means_(self) -> np.ndarray:
-        return np.asarray(self._qda("means_")["means"], dtype=np.float64)
+        return np.asarray(self._qda("means_", ("qda", "lda"))["means"], dtype=np.float64)
 
     @property
     def priors_(self) -> np.ndarray:
-        return np.asarray(self._qda("priors_")["priors"], dtype=np.float64)
+        return np.asarray(self._qda("priors_", ("qda", "lda"))["priors"], dtype=np.float64)
 
     @property
     def rotations_(self) -> list:
@@ -372,11 +387,26 @@ class Predictor:
         return [np.asarray(m["scalings"][c], dtype=np.float64)[:int(k)] for c, k in enumerate(m["n_kept"])]
 
     @property
+    def covariance_(self) -> np.ndarray:
+        """LinearDiscriminantAnalysis: the pooled within-class covariance (lsqr and eigen: the
+        shrunk one the coefficients solve; svd: only when fitted with store_covariance)."""
+        v = self._qda("covariance_", ("lda",)).get("covariance")
+        if v is None:
+            raise AttributeError(f"{self.model_type} artefact has no covariance_ (svd without store_covariance)")
+        return np.asarray(v, dtype=np.float64)
+
+    @property
     def coef_(self) -> np.ndarray:
+        if self.kind == "lda":   # two classes: sklearn keeps the difference, shape (1, d)
+            W = np.asarray(self.model["coef"], dtype=np.float64)
+            return (W[1] - W[0])[None, :] if W.shape[0] == 2 else W
         return np.asarray(self._linreg("coef_")["coef"], dtype=np.float64)
 
     @property
-    def intercept_(self) -> float:
+    def intercept_(self):
+        if self.kind == "lda":
+            b = np.asarray(self.model["intercept"], dtype=np.float64)
+            return (b[1:] - b[:1]) if b.shape[0] == 2 else b
         return float(self._linreg("intercept_")["intercept"])
 
     @property

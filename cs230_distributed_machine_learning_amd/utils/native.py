@@ -178,6 +178,14 @@ QdaScoreArgs = _i64_struct(
     ["X", "ld", "n", "d", "rows", "row_off", "S", "max_rows", "total_rows", "C", "NC", "mu", "V", "inv", "cst", "pred",
      "dec"],
 )
+# csrc/kernels/lda_args.h (LinearDiscriminantAnalysis: lda.hip)
+LdaStatArgs = _i64_struct(
+    "LdaStatArgs",
+    ["X", "ld", "n", "d", "perm", "cell_off", "n_cells", "C", "train", "S", "mean", "w", "parts", "part", "out"])
+LdaScoreArgs = _i64_struct(
+    "LdaScoreArgs",
+    ["X", "ld", "n", "d", "rows", "row_off", "S", "max_rows", "total_rows", "C", "NC", "NCp", "W", "b", "pred", "dec"])
+LDA_TOO_LARGE = 3      # dml_lda_*: d, the split or the candidate count above the kernel's limit, nothing was launched
 QDA_TOO_LARGE = 3      # dml_qda_*: d or the candidate count above the kernel's limit, nothing was launched
 ENET_D_TOO_LARGE = 3   # dml_enet_cd: d above dml_enet_max_d(), nothing was launched
 LrGradArgs = _i64_struct("LrGradArgs", ["rh", "rl", "unused", "xth", "xtl", "m_tiles", "n_tiles", "Kp", "S", "Kc", "out",
@@ -417,6 +425,13 @@ def _register_optional(lib) -> None:
         "dml_qda_max_candidates": (c_i32, []),
         "dml_qda_class_moments": (c_i32, [ctypes.POINTER(QdaMomArgs), c_vp]),
         "dml_qda_score": (c_i32, [ctypes.POINTER(QdaScoreArgs), c_vp]),
+        "dml_lda_sizeof_stat_args": (c_i32, []),
+        "dml_lda_sizeof_score_args": (c_i32, []),
+        "dml_lda_max_d": (c_i32, []),
+        "dml_lda_max_candidates": (c_i32, []),
+        "dml_lda_max_splits": (c_i32, []),
+        "dml_lda_lw_stat": (c_i32, [ctypes.POINTER(LdaStatArgs), c_vp]),
+        "dml_lda_score": (c_i32, [ctypes.POINTER(LdaScoreArgs), c_vp]),
     }
     for name, (res, args) in table.items():
         fn = getattr(lib, name, None)
@@ -446,6 +461,10 @@ def _register_optional(lib) -> None:
             and (lib.dml_qda_sizeof_mom_args() != ctypes.sizeof(QdaMomArgs)
                  or lib.dml_qda_sizeof_score_args() != ctypes.sizeof(QdaScoreArgs))):
         raise RuntimeError("QDA argument layout mismatch between HIP library and Python")
+    if (getattr(lib, "dml_lda_sizeof_stat_args", None) is not None
+            and (lib.dml_lda_sizeof_stat_args() != ctypes.sizeof(LdaStatArgs)
+                 or lib.dml_lda_sizeof_score_args() != ctypes.sizeof(LdaScoreArgs))):
+        raise RuntimeError("LDA argument layout mismatch between HIP library and Python")
     if (getattr(lib, "dml_svm_dec_sizeof_args", None) is not None
             and lib.dml_svm_dec_sizeof_args() != ctypes.sizeof(SvmDecArgs)):
         raise RuntimeError("SvmDecArgs layout mismatch between HIP library and Python")
