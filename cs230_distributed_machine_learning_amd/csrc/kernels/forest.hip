@@ -124,6 +124,22 @@ template <int MODE> constexpr int block_nt() { return MODE == 1 ? DML_BLOCK_NT :
 // docs/SUBTREE_PK16.md)
 #define DML_SUB_PK16 1
 #endif
+#ifndef DML_SUB_POST
+// the packed paths' code after the sort, for the Gini criterion (docs/SUBTREE_POST.md): 1 evaluates
+// both key halves in one pass -- segment-local DPP weight scans against the node's totals (taken
+// once per node, not per pass by readlanes), and ONE u64 max over both halves' scores with the low
+// half winning a tie, which is the sequential outcome.  0: one half after the other, as before.
+// The -DDML_X2_POST sensitivity builds double links of the one-half-at-a-time code, which Gini
+// builds run only with DML_SUB_POST=0: they default to it.
+#if defined(DML_X2_POST) && DML_X2_POST != 0
+#define DML_SUB_POST 0
+#else
+#define DML_SUB_POST 1
+#endif
+#endif
+#if defined(DML_X2_POST) && DML_X2_POST != 0 && DML_SUB_POST != 0
+#error "DML_X2_POST instruments sub_post_pk / seg_post_pk: build it with DML_SUB_POST=0"
+#endif
 #ifndef DML_KGMAX_WAVE
 #define DML_KGMAX_WAVE 4
 #endif
@@ -2356,6 +2372,23 @@ __device__ __forceinline__ void sub_eval(const Ctx& c, const NodeSpec& s, uint64
   bin = bl < 64 ? bsel : -1;
 }
 
+// Sensitivity builds of the code after the packed sort (docs/SUBTREE_POST.md): -DDML_X2_POST=1 runs
+// the weight scan of sub_post_pk / seg_post_pk twice, =2 the fp64 score, =3 the reductions and the
+// selection.  The second run starts from a copy the compiler cannot see through, and its result
+// meets the first in a max of two equal values: the trees are the same trees.  These are the
+// functions of the DML_SUB_POST=0 code (sub_post_pk2 / seg_post_pk2 are not instrumented), so such a
+// build compiles with DML_SUB_POST=0 (see there).
+#ifndef DML_X2_POST
+#define DML_X2_POST 0
+#endif
+#if DML_X2_POST
+template <class T>
+__device__ __forceinline__ T x2_opaque(T v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+#endif
+
 // ---- two features per sort (DML_SUB_PK16): binary classification, no monotonic_cst ---
 // The rows' 16-bit keys of two visiting positions (forest_common.h pk16_key) share a register:
 // the first position in bits 0-15, the second (all absent if there is none) in bits 16-31.
@@ -2380,18 +2413,39 @@ __device__ __forceinline__ void sub_post_pk(const Ctx& c, const NodeSpec& s, int
   const bool cand = valid_row && lane < cnt - 1 && b != bnext && lrows >= s.min_samples_leaf &&
                     rrows >= s.min_samples_leaf;
   const uint32_t w = valid_row ? pk16_w(sk) : 0u;
-  ClsAcc L, R;
-  L.init(s.criterion); R.init(s.criterion);
-  const uint32_t pre = wave::incl_scan<uint32_t>(pk16_scan_word(pk16_cls(sk), w));
-  const uint32_t tot = wave::bcast<uint32_t>(pre, cnt - 1);
-  const uint32_t p1 = pre >> 16, p0 = (pre & 0xFFFFu) - p1, q1 = tot >> 16, q0 = (tot & 0xFFFFu) - q1;
-  const double lw0 = (double)p0 * cwk(cw, 0), tw0 = (double)q0 * cwk(cw, 0);
-  const double lw1 = (double)p1 * cwk(cw, 1), tw1 = (double)q1 * cwk(cw, 1);
-  L.add(lw0); R.add(tw0 - lw0);
-  L.add(lw1); R.add(tw1 - lw1);
-  const bool ok = cand && !side_too_light(s, L.w, R.w);
-  double g = -INFINITY;
-  if (ok) g = cls_proxy(L, R, s.criterion);
+  uint32_t pre = wave::incl_scan<uint32_t>(pk16_scan_word(pk16_cls(sk), w));
+  uint32_t tot = wave::bcast<uint32_t>(pre, cnt - 1);
+#if DML_X2_POST == 1   // sensitivity build: the scan twice
+  {
+    const uint32_t pre2 = wave::incl_scan<uint32_t>(x2_opaque(pk16_scan_word(pk16_cls(sk), w)));
+    const uint32_t tot2 = wave::bcast<uint32_t>(pre2, cnt - 1);
+    pre = max(pre, pre2); tot = max(tot, tot2);
+  }
+#endif
+  bool ok;
+  auto score = [&](uint32_t pre, uint32_t tot) {
+    ClsAcc L, R;
+    L.init(s.criterion); R.init(s.criterion);
+    const uint32_t p1 = pre >> 16, p0 = (pre & 0xFFFFu) - p1, q1 = tot >> 16, q0 = (tot & 0xFFFFu) - q1;
+    const double lw0 = (double)p0 * cwk(cw, 0), tw0 = (double)q0 * cwk(cw, 0);
+    const double lw1 = (double)p1 * cwk(cw, 1), tw1 = (double)q1 * cwk(cw, 1);
+    L.add(lw0); R.add(tw0 - lw0);
+    L.add(lw1); R.add(tw1 - lw1);
+    ok = cand && !side_too_light(s, L.w, R.w);
+    double g = -INFINITY;
+    if (ok) g = cls_proxy(L, R, s.criterion);
+    return g;
+  };
+  double g = score(pre, tot);
+#if DML_X2_POST == 2   // sensitivity build: the score twice
+  g = fmax(g, score(x2_opaque(pre), tot));
+#endif
+#if DML_X2_POST == 3   // sensitivity build: the reduction and selection twice
+  const double g_in = g;
+  for (int rep = 0; rep < 2; ++rep) {
+  const double gprev = g;
+  g = x2_opaque(g_in);
+#endif
   int bl;
   if (s.criterion == kGini) {   // positive doubles order like their bit patterns (see sub_eval)
     const uint64_t gb = ok ? __builtin_bit_cast(uint64_t, g) : 0ull;
@@ -2408,7 +2462,75 @@ __device__ __forceinline__ void sub_post_pk(const Ctx& c, const NodeSpec& s, int
   }
   gain = g;
   const int bsel = wave::bcast<int>(b, bl & 63);
+#if DML_X2_POST == 3
+  bin = rep ? max(bin, bl < 64 ? bsel : -1) : (bl < 64 ? bsel : -1);
+  if (rep) gain = fmax(gain, gprev);
+  }
+#else
   bin = bl < 64 ? bsel : -1;
+#endif
+}
+
+// u64 max over the wave (Gini scores as bit patterns, see sub_eval)
+__device__ __forceinline__ uint64_t wave_max_u64(uint64_t mx, int lane) {
+#define DML_MAXU64_STEP(M) { const uint64_t o = wave::shfl_xor<M>(mx, lane); mx = o > mx ? o : mx; }
+  DML_MAXU64_STEP(32) DML_MAXU64_STEP(16) DML_MAXU64_STEP(8) DML_MAXU64_STEP(4) DML_MAXU64_STEP(2) DML_MAXU64_STEP(1)
+#undef DML_MAXU64_STEP
+  return mx;
+}
+
+// sub_post_pk for BOTH halves of a packed sort and the caller's two sequential updates of the
+// running best (DML_SUB_POST, Gini only): the low half is visiting position pos (feature f0), the
+// high half pos + 1 (f1, absent keys unless has2).  Sequentially the low half's best candidate
+// replaces the running best if strictly greater, then -- if max_features still has room -- the high
+// half's if strictly greater than that.  Here every lane takes the larger of its two scores, one
+// u64 max runs over the wave, and the low half wins a tie: with Glo, Ghi the halves' maxima, the
+// low half is chosen iff Glo >= Ghi and Glo > best, the high half iff Ghi > Glo and Ghi > best,
+// which is what the two updates in order give.  Within a half the lowest lane holding the maximum
+// is the lowest bin, as in sub_post_pk.  The weight totals are those of the node, one readlane.
+__device__ __forceinline__ void sub_post_pk2(const Ctx& c, const NodeSpec& s, int cnt, int lane, uint32_t sk, bool has2,
+                                             int f0, int f1, int& nonconst, double& best_g, int& best_f, int& best_b,
+                                             const double* cw) {
+  const bool valid_row = lane < cnt;
+  const uint32_t skn = wave::shift_down1<uint32_t>(sk, lane, 0u);
+  const uint32_t dends = wave::bcast<uint32_t>(sk, 0) ^ wave::bcast<uint32_t>(sk, cnt - 1);
+  const bool nc_lo = pk16_bin(dends & 0xFFFFu) != 0, nc_hi = pk16_bin(dends >> 16) != 0;
+  const int n_lo = nonconst + (nc_lo ? 1 : 0);
+  const bool use_hi = has2 && n_lo < s.max_features;
+  nonconst = n_lo + ((use_hi && nc_hi) ? 1 : 0);
+  const int lrows = lane + 1, rrows = cnt - lrows;
+  const bool inner = lane < cnt - 1 && lrows >= s.min_samples_leaf && rrows >= s.min_samples_leaf;
+  const uint32_t dx = sk ^ skn;
+  const bool cand_lo = inner && pk16_bin(dx & 0xFFFFu) != 0, cand_hi = use_hi && inner && pk16_bin(dx >> 16) != 0;
+  const uint32_t k_lo = sk & 0xFFFFu, k_hi = sk >> 16;
+  const uint32_t pre_lo = wave::incl_scan<uint32_t>(pk16_scan_word(pk16_cls(k_lo), valid_row ? pk16_w(k_lo) : 0u));
+  const uint32_t pre_hi = wave::incl_scan<uint32_t>(pk16_scan_word(pk16_cls(k_hi), valid_row ? pk16_w(k_hi) : 0u));
+  const uint32_t tot = wave::bcast<uint32_t>(pre_lo, cnt - 1);
+  const uint32_t q1 = tot >> 16, q0 = (tot & 0xFFFFu) - q1;
+  const double tw0 = (double)q0 * cwk(cw, 0), tw1 = (double)q1 * cwk(cw, 1);
+  auto score = [&](uint32_t pre, bool cand) {
+    ClsAcc L, R;
+    L.init(kGini); R.init(kGini);
+    const uint32_t p1 = pre >> 16, p0 = (pre & 0xFFFFu) - p1;
+    const double lw0 = (double)p0 * cwk(cw, 0), lw1 = (double)p1 * cwk(cw, 1);
+    L.add(lw0); R.add(tw0 - lw0);
+    L.add(lw1); R.add(tw1 - lw1);
+    const double g = cls_proxy(L, R, kGini);
+    // bit 63: a candidate.  A NaN score (0 / 0 under a zero class weight) is none, as on the host
+    const bool ok = cand && !side_too_light(s, L.w, R.w) && g == g;
+    return ok ? __builtin_bit_cast(uint64_t, g) | (1ull << 63) : 0ull;
+  };
+  const uint64_t gb_lo = score(pre_lo, cand_lo), gb_hi = score(pre_hi, cand_hi);
+  const uint64_t mx = wave_max_u64(gb_lo > gb_hi ? gb_lo : gb_hi, lane);
+  const uint64_t hit_lo = __ballot(gb_lo == mx), hit_hi = __ballot(gb_hi == mx);
+  const double g = __builtin_bit_cast(double, mx & ~(1ull << 63));
+  if (mx != 0ull && g > best_g) {
+    const bool hi = hit_lo == 0ull;
+    const uint32_t kw = wave::bcast<uint32_t>(sk, (int)__builtin_ctzll(hi ? hit_hi : hit_lo));
+    best_g = g;
+    best_f = hi ? f1 : f0;
+    best_b = pk16_bin(hi ? kw >> 16 : kw & 0xFFFFu);
+  }
 }
 
 // ---- segmented evaluation of small subtree nodes (classification) -------------------
@@ -2621,25 +2743,55 @@ __device__ __forceinline__ void seg_post_pk(const Ctx& c, const NodeSpec& s, con
   const bool cand = valid_row && j < cnt - 1 && b != bnext && j + 1 >= s.min_samples_leaf &&
                     cnt - j - 1 >= s.min_samples_leaf;
   const bool ncl = valid_row && j < cnt - 1 && b != bnext;
-  double g = -INFINITY;
-  ClsAcc L, R;
-  L.init(s.criterion); R.init(s.criterion);
   // segment-relative inclusive prefix of the packed (all weight | class-1 weight << 16) words
-  uint32_t pre = wave::incl_scan<uint32_t>(pk16_scan_word(pk16_cls(sk), w));
-  uint32_t base = 0, tot = 0;
+  auto scan = [&](uint32_t word, uint32_t& pre, uint32_t& tot) {
+    pre = wave::incl_scan<uint32_t>(word);
+    uint32_t base = 0;
+    tot = 0;
 #pragma unroll
-  for (int q = 0; q < S; ++q) {
-    const uint32_t bq = q ? (uint32_t)__builtin_amdgcn_readlane((int)pre, q * WD - 1) : 0u;
-    const uint32_t eq = (uint32_t)__builtin_amdgcn_readlane((int)pre, q * WD + cnt - 1);
-    if (seg == q) { base = bq; tot = eq - bq; }
+    for (int q = 0; q < S; ++q) {
+      const uint32_t bq = q ? (uint32_t)__builtin_amdgcn_readlane((int)pre, q * WD - 1) : 0u;
+      const uint32_t eq = (uint32_t)__builtin_amdgcn_readlane((int)pre, q * WD + cnt - 1);
+      if (seg == q) { base = bq; tot = eq - bq; }
+    }
+    pre -= base;
+  };
+  uint32_t pre, tot;
+  scan(pk16_scan_word(pk16_cls(sk), w), pre, tot);
+#if DML_X2_POST == 1   // sensitivity build: the segment scan twice
+  {
+    uint32_t pre2, tot2;
+    scan(x2_opaque(pk16_scan_word(pk16_cls(sk), w)), pre2, tot2);
+    pre = max(pre, pre2); tot = max(tot, tot2);
   }
-  pre -= base;
-  const uint32_t l1 = pre >> 16, l0 = (pre & 0xFFFFu) - l1, t1 = tot >> 16, t0 = (tot & 0xFFFFu) - t1;
-  const double lw0 = (double)l0 * cwk(cw, 0), tw0 = (double)t0 * cwk(cw, 0);
-  const double lw1 = (double)l1 * cwk(cw, 1), tw1 = (double)t1 * cwk(cw, 1);
-  L.add(lw0); R.add(tw0 - lw0);
-  L.add(lw1); R.add(tw1 - lw1);
-  if (cand && !side_too_light(s, L.w, R.w)) g = cls_proxy(L, R, s.criterion);
+#endif
+  auto score = [&](uint32_t pre, uint32_t tot) {
+    ClsAcc L, R;
+    L.init(s.criterion); R.init(s.criterion);
+    const uint32_t l1 = pre >> 16, l0 = (pre & 0xFFFFu) - l1, t1 = tot >> 16, t0 = (tot & 0xFFFFu) - t1;
+    const double lw0 = (double)l0 * cwk(cw, 0), tw0 = (double)t0 * cwk(cw, 0);
+    const double lw1 = (double)l1 * cwk(cw, 1), tw1 = (double)t1 * cwk(cw, 1);
+    L.add(lw0); R.add(tw0 - lw0);
+    L.add(lw1); R.add(tw1 - lw1);
+    double g = -INFINITY;
+    if (cand && !side_too_light(s, L.w, R.w)) g = cls_proxy(L, R, s.criterion);
+    return g;
+  };
+  double g = score(pre, tot);
+#if DML_X2_POST == 2   // sensitivity build: the score twice
+  g = fmax(g, score(x2_opaque(pre), tot));
+#endif
+#if DML_X2_POST == 3   // sensitivity build: the reductions and the selection twice (the first into copies)
+  const double g_in = g;
+  const int nc_in = nonconst;
+  const double bg_in = best_g;
+  const int bf_in = best_f, bb_in = best_b;
+  int nc_1 = 0, bf_1 = 0, bb_1 = 0;
+  double bg_1 = 0.0;
+  for (int rep = 0; rep < 2; ++rep) {
+  if (rep) { nc_1 = nonconst; bg_1 = best_g; bf_1 = best_f; bb_1 = best_b; nonconst = nc_in; best_g = bg_in; best_f = bf_in; best_b = bb_in; }
+  g = x2_opaque(g_in);
+#endif
   const bool ok = g != -INFINITY;
   int bl = ok ? j : 64;
   argmax_seg<WD>(g, bl, lane);
@@ -2670,6 +2822,86 @@ __device__ __forceinline__ void seg_post_pk(const Ctx& c, const NodeSpec& s, con
     best_f = feature_at(fp, pos + qi, d);
     best_b = __builtin_amdgcn_readlane(bsel, qi * WD);
   }
+#if DML_X2_POST == 3
+  }
+  nonconst = max(nonconst, nc_1); best_g = fmax(best_g, bg_1); best_f = max(best_f, bf_1); best_b = max(best_b, bb_1);
+#endif
+}
+
+// seg_post_pk for BOTH key halves of a packed sort (DML_SUB_POST, Gini only): the low halves are the
+// visiting positions pos .. pos + S - 1, the high halves pos + S .. pos + 2 S - 1, and the result is
+// that of seg_post_pk on the low halves followed by seg_post_pk on the high halves.
+//  * tot: the node's packed weight totals.  Every segment and half holds the node's rows, so its
+//    totals are the node's: the caller takes them once per node, and the prefixes come from a
+//    segment-local scan (wave_ops.h incl_scan_seg) -- no readlanes per pass.
+//  * Counting: a feature counts if it is non-constant and fewer than `room` non-constant features
+//    precede it.  The high halves' room is what the low halves leave; if that is none, or there is
+//    no position pos + S, no high half counts -- the conditions under which the second
+//    seg_post_pk is not run.
+//  * Selection: seg_post_pk takes the first maximum in visiting order (then the lowest bin) among
+//    the counted features, and it replaces the running best if strictly greater.  Lane order is
+//    (segment, bin rank), so within one half that is the lowest lane holding the wave's maximum.
+//    Across halves every low-half position precedes every high-half one, and run in sequence the
+//    high halves win only with a score strictly above the low halves' maximum: the low half wins
+//    a tie.  Hence one u64 max over the lanes' larger scores (Gini scores as bit patterns, see
+//    sub_eval; bit 63 marks a candidate), two ballots, and the lowest lane of the low hits, else of
+//    the high hits.
+template <int WD>
+__device__ __forceinline__ void seg_post_pk2(const Ctx& c, const NodeSpec& s, const FeatPerm& fp, int cnt, int lane, uint32_t sk,
+                                             uint32_t tot, int pos, int& nonconst, double& best_g, int& best_f,
+                                             int& best_b, const double* cw PH_ARGS_DECL) {
+  constexpr int S = 64 / WD;
+  const int d = c.d;
+  const int seg = lane / WD, j = lane & (WD - 1);
+  const bool valid_row = j < cnt;
+  // a lane ends a bin run of a half if its successor (a row of the node) has another bin there
+  const uint32_t dx = sk ^ wave::shift_down1<uint32_t>(sk, lane, 0u);
+  const bool inner = j < cnt - 1;
+  const bool ncl_lo = inner && pk16_bin(dx & 0xFFFFu) != 0, ncl_hi = inner && pk16_bin(dx >> 16) != 0;
+  const bool leaf_ok = j + 1 >= s.min_samples_leaf && cnt - j - 1 >= s.min_samples_leaf;
+  const uint64_t ncm_lo = __ballot(ncl_lo), ncm_hi = __ballot(ncl_hi);
+  uint32_t ncs_lo = 0, ncs_hi = 0;   // bit q: segment q's feature is non-constant (and exists)
+#pragma unroll
+  for (int q = 0; q < S; ++q) {
+    if (pos + q < d && ((ncm_lo >> (q * WD)) & ((1ull << WD) - 1ull)) != 0ull) ncs_lo |= 1u << q;
+    if (pos + S + q < d && ((ncm_hi >> (q * WD)) & ((1ull << WD) - 1ull)) != 0ull) ncs_hi |= 1u << q;
+  }
+  const int n_lo = min(s.max_features, nonconst + __popc(ncs_lo));
+  const uint32_t below = (1u << seg) - 1u;
+  const bool cnt_lo = ((ncs_lo >> seg) & 1u) && __popc(ncs_lo & below) < s.max_features - nonconst;
+  const bool cnt_hi = ((ncs_hi >> seg) & 1u) && __popc(ncs_hi & below) < s.max_features - n_lo;
+  nonconst = min(s.max_features, n_lo + __popc(ncs_hi));
+  const uint32_t t1 = tot >> 16, t0 = (tot & 0xFFFFu) - t1;
+  const double tw0 = (double)t0 * cwk(cw, 0), tw1 = (double)t1 * cwk(cw, 1);
+  auto score = [&](uint32_t k, bool cand) {
+    const uint32_t pre = wave::incl_scan_seg<WD>(pk16_scan_word(pk16_cls(k), valid_row ? pk16_w(k) : 0u), j);
+    ClsAcc L, R;
+    L.init(kGini); R.init(kGini);
+    const uint32_t l1 = pre >> 16, l0 = (pre & 0xFFFFu) - l1;
+    const double lw0 = (double)l0 * cwk(cw, 0), lw1 = (double)l1 * cwk(cw, 1);
+    L.add(lw0); R.add(tw0 - lw0);
+    L.add(lw1); R.add(tw1 - lw1);
+    const double g = cls_proxy(L, R, kGini);
+    // a NaN score (0 / 0: a side that holds only a class of weight zero) is no candidate, as on the
+    // host, where `g > best` is false for it; its bit pattern would win the max over both halves
+    const bool ok = cand && !side_too_light(s, L.w, R.w) && g == g;
+    return ok ? __builtin_bit_cast(uint64_t, g) | (1ull << 63) : 0ull;
+  };
+  const uint64_t gb_lo = score(sk & 0xFFFFu, cnt_lo && ncl_lo && leaf_ok);
+  const uint64_t gb_hi = score(sk >> 16, cnt_hi && ncl_hi && leaf_ok);
+  PH(5)
+  const uint64_t mx = wave_max_u64(gb_lo > gb_hi ? gb_lo : gb_hi, lane);
+  const uint64_t hit_lo = __ballot(gb_lo == mx), hit_hi = __ballot(gb_hi == mx);
+  const double g = __builtin_bit_cast(double, mx & ~(1ull << 63));
+  if (mx != 0ull && g > best_g) {
+    const bool hi = hit_lo == 0ull;
+    const int wl = (int)__builtin_ctzll(hi ? hit_hi : hit_lo);
+    const uint32_t kw = wave::bcast<uint32_t>(sk, wl);
+    best_g = g;
+    best_f = feature_at(fp, pos + (hi ? S : 0) + wl / WD, d);
+    best_b = pk16_bin(hi ? kw >> 16 : kw & 0xFFFFu);
+  }
+  PH(6)
 }
 
 // sub_node_seg for binary classification with 2 S features per pass: segment q's low key half
@@ -2679,7 +2911,7 @@ __device__ __forceinline__ void seg_post_pk(const Ctx& c, const NodeSpec& s, con
 template <int WD>
 __device__ __forceinline__ void sub_node_seg_pk(const Ctx& c, const NodeSpec& s, const FeatPerm& fp, int cnt, int lane, int src,
                                                 int cls_j, uint32_t w_j, const uint8_t* xc, int dp, int& nonconst,
-                                                double& best_g, int& best_f, int& best_b, const double* cw) {
+                                                double& best_g, int& best_f, int& best_b, const double* cw PH_ARGS_DECL) {
   static_assert(WD == 8 || WD == 16 || WD == 32, "segments of 8, 16 or 32 lanes");
   constexpr int S = 64 / WD;
   const int d = c.d;
@@ -2688,6 +2920,15 @@ __device__ __forceinline__ void sub_node_seg_pk(const Ctx& c, const NodeSpec& s,
   const uint32_t pay = pk16_key(0, cls_j, w_j);
   // the first 64 visiting positions, one per lane (see sub_node_seg)
   const int fo = feature_at(fp, min(lane, d - 1), d);
+#if DML_SUB_POST
+  // Gini: both halves in one pass (seg_post_pk2) against the node's weight totals -- segment 0's
+  // rows in compact order, scanned once
+  const bool post2 = s.criterion == kGini;
+  uint32_t tot = 0;
+  if (post2)
+    tot = wave::bcast<uint32_t>(
+        wave::incl_scan_seg<WD>(valid_row ? pk16_scan_word(pk16_cls(pay), pk16_w(pay)) : 0u, j), cnt - 1);
+#endif
   for (int pos = 0; nonconst < s.max_features && pos < d; pos += 2 * S) {
     const bool has_lo = pos + seg < d, has_hi = pos + S + seg < d;
     int flo = 0, fhi = 0;
@@ -2708,9 +2949,17 @@ __device__ __forceinline__ void sub_node_seg_pk(const Ctx& c, const NodeSpec& s,
     const uint32_t key = valid_row ? (((bin_lo << kPk16BinShift) | pay) | (((bin_hi << kPk16BinShift) | pay) << 16))
                                    : (kPk16Absent | (kPk16Absent << 16));
     const uint32_t sk = bitonic_seg_pk16<WD>(key, lane);
+    PH(1)   // phase profile: slot 1 the pass set-up and sort, 5 counting, scans and scores, 6 the selection
+#if DML_SUB_POST
+    if (post2) {
+      seg_post_pk2<WD>(c, s, fp, cnt, lane, sk, tot, pos, nonconst, best_g, best_f, best_b, cw PH_ARGS_PASS);
+      continue;
+    }
+#endif
     seg_post_pk<WD>(c, s, fp, cnt, lane, sk & 0xFFFFu, pos, nonconst, best_g, best_f, best_b, cw);
     if (nonconst < s.max_features && pos + S < d)
       seg_post_pk<WD>(c, s, fp, cnt, lane, sk >> 16, pos + S, nonconst, best_g, best_f, best_b, cw);
+    PH(6)   // the old code's halves are not split further: scans, scores and selection together
   }
 }
 
@@ -2756,9 +3005,9 @@ __device__ __forceinline__ void subtree_dfs(const Ctx& c, const NodeSpec& s, int
         double bg2 = best_g;
         if (pk16_seg) {
           if constexpr (!REG) {
-            if (cnt <= 8) sub_node_seg_pk<8>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nc2, bg2, bf2, bb2, tcw);
-            else if (cnt <= 16) sub_node_seg_pk<16>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nc2, bg2, bf2, bb2, tcw);
-            else sub_node_seg_pk<32>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nc2, bg2, bf2, bb2, tcw);
+            if (cnt <= 8) sub_node_seg_pk<8>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nc2, bg2, bf2, bb2, tcw PH_ARGS_PASS);
+            else if (cnt <= 16) sub_node_seg_pk<16>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nc2, bg2, bf2, bb2, tcw PH_ARGS_PASS);
+            else sub_node_seg_pk<32>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nc2, bg2, bf2, bb2, tcw PH_ARGS_PASS);
           }
         } else
         if (cnt <= 8) sub_node_seg<8, REG>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nc2, bg2, bf2, bb2, tcw, yq_j);
@@ -2769,9 +3018,9 @@ __device__ __forceinline__ void subtree_dfs(const Ctx& c, const NodeSpec& s, int
 #endif
       if (pk16_seg) {
         if constexpr (!REG) {
-          if (cnt <= 8) sub_node_seg_pk<8>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nonconst, best_g, best_f, best_b, tcw);
-          else if (cnt <= 16) sub_node_seg_pk<16>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nonconst, best_g, best_f, best_b, tcw);
-          else sub_node_seg_pk<32>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nonconst, best_g, best_f, best_b, tcw);
+          if (cnt <= 8) sub_node_seg_pk<8>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nonconst, best_g, best_f, best_b, tcw PH_ARGS_PASS);
+          else if (cnt <= 16) sub_node_seg_pk<16>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nonconst, best_g, best_f, best_b, tcw PH_ARGS_PASS);
+          else sub_node_seg_pk<32>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nonconst, best_g, best_f, best_b, tcw PH_ARGS_PASS);
         }
       } else
       if (cnt <= 8) sub_node_seg<8, REG>(c, s, fp, cnt, lane, src, cls_j, w_j, xc, dp, nonconst, best_g, best_f, best_b, tcw, yq_j);
@@ -2803,6 +3052,12 @@ __device__ __forceinline__ void subtree_dfs(const Ctx& c, const NodeSpec& s, int
         }
 #endif
         const uint32_t sk = sub_sort_pk2(e.mask, lane, bin0, bin1, has2, my_cls, my_w);
+#if DML_SUB_POST
+        if (s.criterion == kGini) {   // both halves and both updates in one pass
+          sub_post_pk2(c, s, cnt, lane, sk, has2, f0, f1, nonconst, best_g, best_f, best_b, tcw);
+          continue;
+        }
+#endif
         sub_post_pk(c, s, cnt, lane, sk & 0xFFFFu, g, bb, nc, tcw);
         if (nc) {
           ++nonconst;

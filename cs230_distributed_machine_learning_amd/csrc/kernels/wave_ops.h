@@ -113,6 +113,29 @@ __device__ __forceinline__ T incl_scan(T v) {
   return v;
 }
 
+// inclusive prefix sum inside aligned segments of WD = 8, 16 or 32 lanes (j = lane % WD): incl_scan
+// without the steps that cross a segment.  A 16-lane segment is a DPP row; an 8-lane one masks the
+// two lanes a row shift by 1 or 2 would fill from the segment below, and takes the shift by 4 into
+// its upper bank only; a 32-lane one adds row 0's (2's) total to row 1 (3).
+template <int WD>
+__device__ __forceinline__ uint32_t incl_scan_seg(uint32_t v, int j) {
+  static_assert(WD == 8 || WD == 16 || WD == 32, "segments of 8, 16 or 32 lanes");
+  if constexpr (WD == 8) {
+    const uint32_t t1 = dpp<kRowShr + 1>(v);
+    v += j >= 1 ? t1 : 0u;
+    const uint32_t t2 = dpp<kRowShr + 2>(v);
+    v += j >= 2 ? t2 : 0u;
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kRowShr + 4, 0xF, 0xA, true);   // banks 1, 3: lanes 4-7, 12-15
+  } else {
+    v += dpp<kRowShr + 1>(v);
+    v += dpp<kRowShr + 2>(v);
+    v += dpp<kRowShr + 4>(v);
+    v += dpp<kRowShr + 8>(v);
+    if constexpr (WD == 32) v += dpp<kRowBcast15, 0xA>(v);
+  }
+  return v;
+}
+
 // 64-bit unsigned inclusive prefix sum (packed histogram planes)
 template <int CTRL, int RM>
 __device__ __forceinline__ uint64_t scan_step_u64(uint64_t x) {
